@@ -4,6 +4,7 @@ config 4, the default) or the 2048x2048x256 r=16 fp32 workload
 (configs[4] = config 5, ``--config 5``).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--algo admm|als]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 A "step" is one ADMM iteration (triple_decomp_ADMM.m:31-66) over the whole
@@ -11,8 +12,17 @@ tensor, device-resident.  With N > 1 ranks the tensor is sharded along
 mode 1 and the two per-iteration all-reduces run over RCCL
 (strong scaling: the problem size is fixed).  `--gpus N` without a launcher
 starts the N rank processes itself.  Rank 0 prints one JSON
-line.  The CPU baseline is the C restatement of the MATLAB reference
-(oracle/tritd_ref.c, kind "port") timed on a bounded sample on rank 0.
+line.
+
+A plain run does what the headline figure needs and no more: it draws the
+inputs, creates the session, runs W warm-up and K timed iterations, and prints
+the line (iterations/s, ms_per_step, the workload).  `--dump-outputs DIR`
+also writes what the session returns after the last timed iteration (A, B, C,
+O, E, errHist) as DIR/<name>.npy.  Everything else is behind `--full`: the
+HIP-event passes and the roofline, the rest of the 100-iteration solve and its
+RRE, the per-rank breakdown, the end-to-end one-shot calls, the primitive
+kernels, the config-5 leg, and the CPU baseline, which is the C restatement of
+the MATLAB reference (oracle/tritd_ref.c, kind "port") timed on rank 0.
 """
 import argparse
 import json
@@ -387,9 +397,10 @@ def cpu_model():
     return None
 
 
-def make_data(config, n1, n2, n3, r, rows):
+def make_data(config, n1, n2, n3, r, rows, want_L=True):
     """Synthetic inputs of `config`, rows = this rank's
-    mode-1 range; returns (D, Lstar, A0, B0, C0) with D / Lstar of those rows."""
+    mode-1 range; returns (D, Lstar, A0, B0, C0) with D / Lstar of those rows
+    (Lstar None unless wanted: a plain run never reads it)."""
     from tritd import synth
     i0, i1 = rows
     if config == 2:  # RRE against the complete readings (traffic_triple_comparison.m:62)
@@ -405,16 +416,43 @@ def make_data(config, n1, n2, n3, r, rows):
     else:
         d = synth.low_rank_plus_outliers(n1, n2, n3, r, p_out=0.05, seed=0, init_seed=123)
     D = np.asfortranarray(d["D"][i0:i1], dtype=np.float64)
-    L = np.asfortranarray(d["Lstar"][i0:i1], dtype=np.float64)
+    L = np.asfortranarray(d["Lstar"][i0:i1], dtype=np.float64) if want_L else None
     return D, L, d["A0"], d["B0"], d["C0"]
 
 
-def run_case(config, K, W, group, comm, local_rank, n=None, r=None, host_comm=False):
+DUMP_SAMPLE = 1 << 21  # elements kept of an output too large to dump whole
+DUMP_WHOLE_BYTES = 16 << 20  # O and E are dumped whole up to this size each
+
+
+def dump_outputs(out_dir, res, rank, world):
+    """--dump-outputs: what Session.get() returned after the last timed
+    iteration, as <out_dir>/<name>.npy in the arrays' own precision (float32 or
+    float64; `_rank<r>` appended to the name at N > 1, each rank writing its
+    shard).  The factors and errHist are written whole; O and E are written
+    whole up to 16 MiB each, otherwise as the elements (in column-major order)
+    at 2^21 sorted indices drawn from numpy's default_rng(0): the same
+    elements on every run of the same shape, 32 MiB at most for the pair."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for name in ("A", "B", "C", "O", "E", "errHist"):
+        a = np.asarray(res[name])
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if name in ("O", "E") and a.nbytes > DUMP_WHOLE_BYTES:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=DUMP_SAMPLE))
+            a = a.ravel(order="K")[idx]  # (O and E are column-major: a view, no copy)
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
+def run_case(config, K, W, group, comm, local_rank, n=None, r=None, host_comm=False, full=True,
+             dump_dir=None):
     """One sharded (or single-GPU) run of `config`: W untimed warm-up
-    iterations, K timed iterations between barriers (max over ranks), a K5
-    events pass, an events sample, then the untimed rest of the 100-iteration
-    solve and the driver's RRE.  Returns (result dict, (D, Lstar, A0, B0, C0))
-    — the data of this rank's rows, for the rank-0 extras."""
+    iterations, K timed iterations between barriers (max over ranks), the
+    outputs after the last of them written to `dump_dir` if given, and — with
+    `full` — a K5 events pass, an events sample, then the untimed rest of the
+    100-iteration solve and the driver's RRE.  Returns (result dict,
+    (D, Lstar, A0, B0, C0)) — the data of this rank's rows, for the rank-0
+    extras (Lstar None without `full`)."""
     import tritd
     from tritd import hip, synth
     from tritd.dist import shard_bounds
@@ -428,9 +466,13 @@ def run_case(config, K, W, group, comm, local_rank, n=None, r=None, host_comm=Fa
     npdt = np.float32 if f32 else np.float64
     maxIter = max(100, K + W)
     base_opts = synth.VIDEO_OPTS if config == 3 else synth.TRAFFIC_OPTS
-    opts = dict(base_opts, maxIter=maxIter, tol=base_opts["tol"])
+    # up to the drivers' 100 iterations the stop test keeps their tol (it does
+    # not fire there); a longer run iterates past it (tol 0: the test is still
+    # computed every iteration, it only never stops the solve), so --steps
+    # sets the number of timed iterations at any K
+    opts = dict(base_opts, maxIter=maxIter, tol=base_opts["tol"] if K + W <= 100 else 0.0)
     i0, i1 = shard_bounds(n1, world, rank)
-    D, Lstar, A0, B0, C0 = make_data(config, n1, n2, n3, rr, (i0, i1))
+    D, Lstar, A0, B0, C0 = make_data(config, n1, n2, n3, rr, (i0, i1), want_L=full)
 
     def barrier():
         if group:
@@ -467,6 +509,18 @@ def run_case(config, K, W, group, comm, local_rank, n=None, r=None, host_comm=Fa
     dt, done, stopped = timed(K)
     if done != W + K or stopped:
         raise SystemExit("stop test fired inside the timed region (k=%d): timing invalid" % done)
+    if dump_dir:
+        dump_outputs(dump_dir, sess.get(), rank, world)
+    out = {
+        "value": K / dt, "ms_per_step": dt * 1e3 / K, "steps": K, "warmup": W, "dtype": dts,
+        "n1": n1, "n2": n2, "n3": n3, "r": rr, "maxIter": maxIter, "opts": opts,
+        "workload": (WORKLOADS[config] if n is None and r is None
+                     else "config %d shape override: %dx%dx%d r=%d"
+                     % (config, n1, n2, n3, rr)).replace("%%", "%"),
+    }
+    if not full:
+        sess.close()
+        return out, (D, Lstar, A0, B0, C0)
     dense1, _ = sess.counters()
     dense_per_launch = (dense1 - dense0) / K
     # K5's launch duration for the roofline: HIP events around K5 only, on
@@ -564,12 +618,7 @@ def run_case(config, K, W, group, comm, local_rank, n=None, r=None, host_comm=Fa
                          "algorithmic_flops_per_launch": k2_flops, "ms": k2_ms,
                          "pmc_mfma_util": pmc_util, "pmc_source": pmc_src}
     sess.close()
-    out = {
-        "value": K / dt, "ms_per_step": dt * 1e3 / K, "steps": K, "warmup": W, "dtype": dts,
-        "n1": n1, "n2": n2, "n3": n3, "r": rr, "maxIter": maxIter, "opts": opts,
-        "workload": (WORKLOADS[config] if n is None and r is None
-                     else "config %d shape override: %dx%dx%d r=%d"
-                     % (config, n1, n2, n3, rr)).replace("%%", "%"),
+    out.update({
         "per_rank": per_rank, "rre_final": rre, "k_final": k_final,
         "errHist_final": errhist_final,
         "kernel_ms": {"fused_update": k5_ms, "mode3_mttkrp": km["mode3"],
@@ -580,7 +629,7 @@ def run_case(config, K, W, group, comm, local_rank, n=None, r=None, host_comm=Fa
                                                  "without events)"}},
         "roofline": roof,
         "placement_probe": {"ms": [round(m, 4) for m in probe_ms], "picked": probe_pick},
-    }
+    })
     return out, (D, Lstar, A0, B0, C0)
 
 
@@ -629,6 +678,14 @@ def main():
                     help="config 4: cube side override (--side under torchrun, whose own "
                          "parser takes --n for an abbreviation of its options)")
     ap.add_argument("--r", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs after the last timed step (A, B, C, O, E, errHist) "
+                         "as DIR/<name>.npy; O and E as a fixed seeded sample when large")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: HIP-event passes and "
+                         "roofline, the rest of the solve and its RRE, end-to-end calls, primitive "
+                         "kernels, the config-5 leg and the CPU baseline (each with its --no-* "
+                         "switch)")
     # the full 100-iteration solve at configs 1-4 (one
     # iteration at config 5, reported per iteration)
     ap.add_argument("--cpu-iters", type=int, default=None)
@@ -699,16 +756,18 @@ def main():
         raise SystemExit("communicator reports %d ranks, WORLD_SIZE is %d" % (comm_info[0], world))
 
     main_res, data = run_case(args.config, args.steps, args.warmup, group, comm, local_rank,
-                              n=args.n, r=args.r, host_comm=host_comm)
+                              n=args.n, r=args.r, host_comm=host_comm, full=args.full,
+                              dump_dir=args.dump_outputs)
     D, Lstar, A0, B0, C0 = data
+    extras = args.full and rank == 0 and world == 1
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if extras and not args.no_e2e:
         e2e = end_to_end(tritd, D, main_res["r"], main_res["opts"], A0, B0, C0, local_rank)
     prims = None
-    if rank == 0 and world == 1 and not args.no_prims:
+    if extras and not args.no_prims:
         prims = primitives(local_rank)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if extras and not args.no_cpu:
         f32 = CONFIGS[args.config][4] == "f32"
         iters = args.cpu_iters if args.cpu_iters is not None else (1 if f32 else 100)
         cpu = cpu_baseline(D, main_res["r"], main_res["opts"], A0, B0, C0, iters,
@@ -719,7 +778,7 @@ def main():
     # r4 next 5, r5 next 3b): a bounded config-5 run on the same ranks and
     # communicator, after the config-4 session has released its device memory
     c5 = None
-    if args.config == 4 and args.n is None and args.r is None and not args.no_c5:
+    if args.full and args.config == 4 and args.n is None and args.r is None and not args.no_c5:
         d5, _ = run_case(5, args.c5_steps, 2, group, comm, local_rank, host_comm=host_comm)
         c5 = config5_summary(d5)
 
@@ -740,6 +799,7 @@ def main():
             "config": {"workload": main_res["workload"],
                        "n1": main_res["n1"], "n2": main_res["n2"], "n3": main_res["n3"],
                        "r": main_res["r"], "maxIter": main_res["maxIter"],
+                       "tol": main_res["opts"]["tol"],
                        "parallelism": "mode1-shard x%d" % world
                                       + (" (host all-reduce rehearsal: not a scaling number)"
                                          if host_comm and world > 1 else "")},
@@ -750,6 +810,10 @@ def main():
             # HIP / HSA / RCCL copies mapped in rank 0 (one each, /opt/rocm)
             "runtime_stack": runtime_stack(),
             "rccl_nranks": comm_info[0] if comm_info[2] == "rccl" else None,
+            "full": args.full,
+        }
+    if rank == 0 and args.full:
+        line.update({
             # N > 1: per rank, from an events sample after the timed region
             "per_rank": main_res["per_rank"],
             "rre_final": main_res["rre_final"],
@@ -771,7 +835,8 @@ def main():
             "primitives": prims,
             # config 5 (2048x2048x256 fp32 r=16) on the same ranks, a bounded run
             "config5": c5,
-        }
+        })
+    if rank == 0:
         print(json.dumps(line), flush=True)
 
     if comm is not None:
@@ -834,12 +899,17 @@ def bench_als(args):
     dt = time.perf_counter() - t0
     km = s.kernel_ms()
     res = s.get()
+    if args.dump_outputs:  # an ALS solve returns the factors and errHist
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name in ("A", "B", "C", "errHist"):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), res[name])
     N = n1 * n2 * n3
     fit_flops = 4.0 * N * r * r
     fit_bytes = N * 8 + r * r * n1 * n2 * 8
     tfs = fit_flops / (km["fit"] * 1e-3) / 1e12 if km["fit"] > 0 else None
-    cpu = None if args.no_cpu else cpu_baseline_als(X, r, data["A0"], data["B0"], data["C0"],
-                                                    args.cpu_iters or 3)
+    cpu = None
+    if args.full and not args.no_cpu:
+        cpu = cpu_baseline_als(X, r, data["A0"], data["B0"], data["C0"], args.cpu_iters or 3)
     line = {
         "metric": "ALS iters/sec (triple_decomp_ALS.m), 512^3 r=8",
         "value": K / dt, "unit": "iters/s", "n_gpus": 1, "steps": K, "warmup": W,
