@@ -86,6 +86,25 @@ def test_als_padded_shapes(tritd, orc, synth, shape, r):
     check(orc, got, *ref)
 
 
+@pytest.mark.parametrize("r", [4, 6, 7])
+def test_als_rank_sweep(tritd, orc, r):
+    """The ranks no other ALS case runs: r = 4 (R = RP = 16, no rank padding),
+    r = 6 (padded rank 48, which nothing else selects) and r = 7 (49 of 64
+    columns), at the ragged shapes of tests/sweep_cases.py (about 35 x 20 x 33;
+    tests/test_sweep_cases.py shows the oracle moves by < 1e-11 there under
+    input rounding).  Measured on an MI355X: A, B, C, L <= 1.5e-14,
+    errHist <= 2.4e-16 relative (r = 6 the largest)."""
+    import sweep_cases as sc
+    c = sc.e_active_case(r)
+    ref = sc.oracle_als_ref(r)
+    got = tritd.triple_decomp_ALS(c["D"], r, sc.ALS_OPTS, c["A0"], c["B0"], c["C0"], return_iters=True)
+    print("  ALS sweep r=%d: A %.1e B %.1e C %.1e L %.1e errHist %.1e" % (
+        r, rel(got[0], ref[0]), rel(got[1], ref[1]), rel(got[2], ref[2]),
+        rel(orc.triple_product(*got[:3]), orc.triple_product(*ref[:3])),
+        np.max(np.abs(got[3] - ref[3]) / ref[3]) if len(got[3]) == len(ref[3]) else np.nan), flush=True)
+    check(orc, got, *ref)
+
+
 def test_als_print_and_opts(tritd, orc):
     g = load_golden("als12x10x8_r2")
     lines = []

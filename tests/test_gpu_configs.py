@@ -171,15 +171,28 @@ def big():
     return d
 
 
-def test_config4_sharded_equals_unsharded(tritd, big):
+def _config4_sharded_equals_unsharded(tritd, big, e_active):
     from tritd import synth
     opts = dict(synth.TRAFFIC_OPTS, maxIter=3)
+    if e_active:  # threshold 2 std(D) instead of 1800: E nonzero within these 3 iterations
+        opts["lambda"] = 2e-3 * float(np.std(big["D"]))
     one = tritd.triple_decomp_ADMM(big["D"], 8, opts, big["A0"], big["B0"], big["C0"],
                                    return_E=True)
     two = tritd.triple_decomp_ADMM(big["D"], 8, opts, big["A0"], big["B0"], big["C0"],
                                    return_E=True, virtual_shards=2)
+    if e_active:
+        assert np.any(one[5]) and np.any(two[5])
     for a, b in zip(one, two):
         assert rel(b, a) <= 1e-11
+
+
+def test_config4_sharded_equals_unsharded(tritd, big):
+    _config4_sharded_equals_unsharded(tritd, big, False)
+
+
+def test_config4_sharded_equals_unsharded_e_active(tritd, big):
+    """With lambda = 1.8 E is identically zero over these 3 iterations; here it is not."""
+    _config4_sharded_equals_unsharded(tritd, big, True)
 
 
 def test_config4_determinism_and_stepping(tritd, big):

@@ -54,21 +54,52 @@ def test_config3_frames_repeat_bitwise(tritd, dense_e):
         _same(_solve(tritd, d["D"], 5, opts, d, env), first)
 
 
-def test_traffic_256_repeat_bitwise(tritd):
+def _active(opts, D, e_active):
+    """lambda = 2e-3 std(D) (threshold 2 std(D) instead of 1800): E is nonzero
+    within the few iterations of these cases.  With lambda = 1.8 it stays
+    identically zero, and the E stores — where a store would be lost — write
+    nothing that a repeat could differ in."""
+    if e_active:
+        opts = dict(opts)
+        opts["lambda"] = 2e-3 * float(np.std(D))
+    return opts
+
+
+def _traffic_256(tritd, e_active):
     from tritd import synth
     d = synth.low_rank_plus_outliers(256, 256, 256, 8, seed=3)
-    opts = dict(synth.TRAFFIC_OPTS, maxIter=4)
+    opts = _active(dict(synth.TRAFFIC_OPTS, maxIter=4), d["D"], e_active)
     first = _solve(tritd, d["D"], 8, opts, d, {})
     _same(_solve(tritd, d["D"], 8, opts, d, {}), first)
+    if e_active:
+        assert np.any(first[5])
 
 
-def test_f32_r16_repeat_bitwise(tritd):
+def test_traffic_256_repeat_bitwise(tritd):
+    _traffic_256(tritd, False)
+
+
+def test_traffic_256_repeat_bitwise_e_active(tritd):
+    _traffic_256(tritd, True)
+
+
+def _f32_r16(tritd, e_active):
     from tritd import synth
     d = synth.low_rank_plus_outliers(256, 256, 64, 16, seed=4)
-    opts = dict(synth.TRAFFIC_OPTS, maxIter=3)
+    opts = _active(dict(synth.TRAFFIC_OPTS, maxIter=3), d["D"], e_active)
     D = d["D"].astype(np.float32)
     first = _solve(tritd, D, 16, opts, d, {})
     _same(_solve(tritd, D, 16, opts, d, {}), first)
+    if e_active:
+        assert np.any(first[5])
+
+
+def test_f32_r16_repeat_bitwise(tritd):
+    _f32_r16(tritd, False)
+
+
+def test_f32_r16_repeat_bitwise_e_active(tritd):
+    _f32_r16(tritd, True)
 
 
 # 96: 6 i-tiles, the two-tile form (k_tp2); 90: the same form with 6 padded

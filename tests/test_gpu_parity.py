@@ -162,12 +162,23 @@ def test_device_set_f32_and_errors(tritd, orc):
             tritd.set_devices([])
 
 
-def test_medium_against_oracle(tritd, orc):
-    """A size with several workgroups per kernel and ragged padding."""
+def _active_lambda(D):
+    """lambda = 2e-3 std(D): with TRAFFIC_OPTS' mu = 1e-3 the soft threshold
+    starts at 2 std(D) instead of 1800, so E is nonzero from the first
+    iterations (with lambda = 1.8 it is identically zero over the few
+    iterations of the cases below, and every comparison of E is 0 == 0)."""
+    return 2e-3 * float(np.std(D))
+
+
+def _medium(tritd, orc, e_active):
     from tritd import synth
     d = synth.low_rank_plus_outliers(70, 33, 50, 8, seed=3)
     opts = dict(synth.TRAFFIC_OPTS, maxIter=6)
+    if e_active:
+        opts["lambda"] = _active_lambda(d["D"])
     ref = orc.triple_decomp_ADMM(d["D"], 8, opts, d["A0"], d["B0"], d["C0"])
+    if e_active:
+        assert np.count_nonzero(ref[5]) >= 0.20 * ref[5].size
     got = tritd.triple_decomp_ADMM(d["D"], 8, opts, d["A0"], d["B0"], d["C0"], return_E=True,
                                    return_iters=True)
     A, B, C, O, eh, E, k = got
@@ -177,11 +188,20 @@ def test_medium_against_oracle(tritd, orc):
     np.testing.assert_allclose(eh, ref[4], rtol=TOL_ERR, atol=ATOL_ERR)
 
 
-@pytest.mark.parametrize("shape,r", [((12, 10), 2), ((5, 1, 7), 2), ((1, 9, 8), 2), ((33, 17, 1), 3),
-                                     ((16, 16, 16), 1)])
-def test_degenerate_shapes_against_oracle(tritd, orc, shape, r):
-    """2-D D (n3 = 1 by MATLAB's trailing-singleton rule), singleton modes and r = 1:
-    ragged single tiles in every padded dimension."""
+def test_medium_against_oracle(tritd, orc):
+    """A size with several workgroups per kernel and ragged padding."""
+    _medium(tritd, orc, False)
+
+
+def test_medium_against_oracle_e_active(tritd, orc):
+    """The same with E active (nnz(E) >= 20 % in the reference)."""
+    _medium(tritd, orc, True)
+
+
+DEGENERATE = [((12, 10), 2), ((5, 1, 7), 2), ((1, 9, 8), 2), ((33, 17, 1), 3), ((16, 16, 16), 1)]
+
+
+def _degenerate(tritd, orc, shape, r, e_active):
     rng = np.random.default_rng(11)
     D = np.asfortranarray(rng.standard_normal(shape) * 3.0)
     n1, n2, n3 = (tuple(shape) + (1,))[:3]
@@ -190,7 +210,11 @@ def test_degenerate_shapes_against_oracle(tritd, orc, shape, r):
     C0 = rng.standard_normal((r, r, n3))
     from tritd import synth
     opts = dict(synth.TRAFFIC_OPTS, maxIter=8)
+    if e_active:
+        opts["lambda"] = _active_lambda(D)
     ref = orc.triple_decomp_ADMM(D, r, opts, A0, B0, C0)
+    if e_active:
+        assert np.count_nonzero(ref[5]) >= 0.20 * ref[5].size
     A, B, C, O, eh, E, k = tritd.triple_decomp_ADMM(D, r, opts, A0, B0, C0, return_E=True,
                                                     return_iters=True)
     assert k == ref[6]
@@ -198,6 +222,20 @@ def test_degenerate_shapes_against_oracle(tritd, orc, shape, r):
     assert rel(O, ref[3]) <= 1e-8
     assert rel(E, ref[5]) <= 1e-8
     np.testing.assert_allclose(eh, ref[4], rtol=1e-7, atol=1e-11)
+
+
+@pytest.mark.parametrize("shape,r", DEGENERATE)
+def test_degenerate_shapes_against_oracle(tritd, orc, shape, r):
+    """2-D D (n3 = 1 by MATLAB's trailing-singleton rule), singleton modes and r = 1:
+    ragged single tiles in every padded dimension."""
+    _degenerate(tritd, orc, shape, r, False)
+
+
+@pytest.mark.parametrize("shape,r", DEGENERATE)
+def test_degenerate_shapes_against_oracle_e_active(tritd, orc, shape, r):
+    """The same shapes with E active (nnz(E) >= 20 % in the reference): the
+    soft threshold and both E storage forms on singleton and ragged modes."""
+    _degenerate(tritd, orc, shape, r, True)
 
 
 def test_disp_prints_like_reference(tritd, orc):
@@ -258,7 +296,12 @@ def test_soft_threshold_bit_exact(tritd, orc):
 # r = 12 and 16 (R = 144 / 256, the padded-rank 256 kernel config 5's
 # reconstruction runs, traffic_triple_comparison.m:62) beside the r <= 8 forms
 @pytest.mark.parametrize("n1,n2,n3,r", [(12, 10, 8, 2), (30, 31, 29, 3), (17, 16, 20, 8), (5, 4, 33, 5),
-                                        (40, 36, 30, 12), (33, 20, 48, 16), (64, 64, 32, 16)])
+                                        (40, 36, 30, 12), (33, 20, 48, 16), (64, 64, 32, 16),
+                                        # every other rank <= 16 at the ragged shapes of
+                                        # tests/sweep_cases.py (r = 6: padded rank 48)
+                                        (36, 23, 33, 4), (35, 20, 35, 6), (36, 21, 36, 7),
+                                        (35, 23, 34, 9), (36, 19, 35, 10), (37, 20, 36, 11),
+                                        (36, 22, 34, 13), (37, 23, 35, 14), (35, 19, 36, 15)])
 def test_triple_product(tritd, orc, n1, n2, n3, r):
     from tritd import synth
     A, B, C = synth.random_factors(n1, n2, n3, r, seed=n1)
@@ -276,6 +319,10 @@ def test_design_matrices_bit_exact(tritd, orc, r):
     np.testing.assert_array_equal(tritd.buildH(A, B), orc.buildH(A, B))
 
 
+# The wide-rank goldens (g20x18x16_r10, g24x20x18_r12, g24x22x20_r16) stop while the
+# threshold lambda/mu is still above every entry: their E is identically zero,
+# so this test pins the factors, L and O at r = 9..16 but not the outlier
+# chain.  tests/test_gpu_rank_sweep.py covers those ranks with E active.
 @pytest.mark.parametrize("name", ["g20x18x16_r10", "g24x22x20_r16"])
 def test_fp64_session_wide_rank_matches_golden(tritd, orc, name):
     """fp64 sessions (the bench / one-process-per-GPU path) take r = 9..16 like

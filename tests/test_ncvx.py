@@ -133,6 +133,31 @@ def test_gpu_ncvx_first_iterations_and_alias(tritd):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("r", [4, 6, 7])
+def test_gpu_ncvx_rank_sweep(tritd, r):
+    """The ranks the goldens leave out (r = 4: no rank padding; r = 6: padded
+    rank 48, selected by nothing else; r = 7: 49 of 64 columns) at the ragged
+    shapes of tests/sweep_cases.py, with the goldens' parameters, against the
+    oracle (which moves by < 1e-11 there under input rounding,
+    tests/test_sweep_cases.py).  Measured on an MI355X: A, B, C, O <= 1.3e-14,
+    errHist <= 4.1e-15 relative (r = 7 the largest)."""
+    import sweep_cases as sc
+    c = sc.e_active_case(r)
+    A, B, C, O, eh, k, _ = sc.oracle_ncvx_ref(r)
+    assert np.any(O)
+    tritd.set_printer(lambda s: None)
+    try:
+        got = tritd.triple_decomp_ncvx(c["D"], r, *sc.ncvx_args(), c["A0"], c["B0"], c["C0"],
+                                       return_iters=True)
+    finally:
+        tritd.set_printer(None)
+    print("  ncvx sweep r=%d: A %.1e B %.1e C %.1e O %.1e errHist %.1e" % (
+        r, rel(got[0], A), rel(got[1], B), rel(got[2], C), rel(got[3], O),
+        np.max(np.abs(got[4] - eh) / eh) if len(got[4]) == len(eh) else np.nan), flush=True)
+    _check(got, dict(A=A, B=B, C=C, O=O, errHist=eh, k=k))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("serial", [False, True])
 def test_gpu_ncvx_device_set(tritd, serial, monkeypatch):
     """Mode-1 shards through tritd_set_devices (one GPU repeated): partial fit

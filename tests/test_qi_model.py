@@ -149,12 +149,41 @@ def test_gpu_qi_virtual_shards(tritd, name, P):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n1,n2,n3,r", [(12, 10, 8, 2), (30, 31, 29, 3), (17, 16, 20, 8),
-                                        (9, 7, 33, 12)])
+                                        (9, 7, 33, 12),
+                                        # ragged shapes of tests/sweep_cases.py at r = 4..7 (r = 6:
+                                        # padded rank 48) and r = 16 (R = 256, no rank padding)
+                                        (36, 23, 33, 4), (37, 19, 34, 5), (35, 20, 35, 6),
+                                        (36, 21, 36, 7), (36, 20, 33, 16)])
 def test_gpu_qi_triple_product(tritd, n1, n2, n3, r):
     A, B, C = _factors(n1, n2, n3, r, seed=3)
     got = tritd.triple_product(A, B, C, "qi")
     assert rel(got, orc.triple_product_qi_loops(A, B, C) if r <= 3 else
                orc.triple_product(A, B, C, "qi")) <= 1e-13
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", [1, 4, 5, 6, 7])
+def test_gpu_qi_rank_sweep_e_active(tritd, r):
+    """The ranks the Qi goldens leave out, on tests/sweep_cases.e_active_case
+    with model='qi': ragged shapes of about 35 x 20 x 33, lambda = 2e-3 std(D)
+    so that E is active from the first iterations (tests/test_sweep_cases.py:
+    nnz(E) 13..70 %, the oracle moves by < 1e-11 under input rounding), against
+    the oracle at this module's tolerances.  Measured on an MI355X: L, O, E <= 1.7e-14;
+    A, B, C <= 5.3e-14 (B at r = 1), <= 1.8e-14 at r >= 4."""
+    import sweep_cases as sc
+    c = sc.e_active_case(r, model="qi")
+    ref = sc.oracle_ref(r, model="qi")
+    nnz = sc.nnz_share(ref["E"])
+    assert sc.NNZ_BAND[0] <= nnz <= sc.NNZ_BAND[1]
+    got = tritd.triple_decomp_ADMM(c["D"], r, c["opts"], c["A0"], c["B0"], c["C0"],
+                                   return_E=True, return_iters=True)
+    print("  qi sweep r=%d nnz(E)=%.3f: L %.1e O %.1e E %.1e A %.1e B %.1e C %.1e" % (
+        r, sc.nnz_share(got[5]),
+        rel(orc.triple_product(*got[:3], "qi"), orc.triple_product(ref["A"], ref["B"], ref["C"], "qi")),
+        rel(got[3], ref["O"]), rel(got[5], ref["E"]), rel(got[0], ref["A"]), rel(got[1], ref["B"]),
+        rel(got[2], ref["C"])), flush=True)
+    assert np.any(got[5])
+    _check(got, ref)
 
 
 @pytest.mark.gpu
