@@ -65,11 +65,12 @@ def _case64(r, model):
 
 
 def e_active_case(r, dtype=np.float64, model="cp"):
-    """dict(D, A0, B0, C0, opts, r): D of `dtype` (column-major), lambda from
-    the fp64 D for either dtype so both precisions solve the same problem."""
+    """dict(D, Lstar, A0, B0, C0, opts, r): D of `dtype` (column-major), lambda
+    from the fp64 D for either dtype so both precisions solve the same problem;
+    Lstar is the generator's low-rank part in fp64 (the driver's RRE reference)."""
     d, opts = _case64(r, model)
-    return dict(D=np.asfortranarray(d["D"], dtype=dtype), A0=d["A0"], B0=d["B0"], C0=d["C0"],
-                opts=dict(opts), r=r)
+    return dict(D=np.asfortranarray(d["D"], dtype=dtype), Lstar=d["Lstar"], A0=d["A0"], B0=d["B0"],
+                C0=d["C0"], opts=dict(opts), r=r)
 
 
 def as_ref(t):

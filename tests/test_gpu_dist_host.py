@@ -11,6 +11,11 @@ for ALS the als.cpp schedule.  Shards are uneven and straddle 16 rows (n1 = 33
 on 2 ranks: 17 | 16; n1 = 49 on 3 ranks: 17 | 16 | 16), so the ranks launch
 different K5 grids.  Results must match the oracle's unsharded solve
 (triple_decomp_ADMM.m:15-68) at the tolerances of test_gpu_parity.py.
+
+With the spec key `full_device` a rank takes its shard the way
+include/tritd.h describes the multi-GPU call — D(i0,0,0) of the whole device
+tensor, ldD = n1 — and reports its rre_parts against L*(i0,0,0); the parent
+checks that the parts sum to the whole.
 """
 import os
 import socket
@@ -78,7 +83,19 @@ def _worker(rank, world, spec, outdir):
     i0, i1 = shard_bounds(n1, world, rank)
     comm = rz_host_comm(group, 0) if dist is None else make_host_comm(dist, rank, world, 0)
     Dl = np.asfortranarray(D[i0:i1])
-    if kind == "admm":
+    dLstar = None
+    if spec.get("full_device"):
+        # the natural multi-GPU call of include/tritd.h: every rank holds the
+        # WHOLE D (and L*) on the device and hands its session D(i0,0,0) with
+        # ldD = n1 (odd i0: a pointer that is only element-aligned)
+        from tritd import hip
+        assert kind == "admm" and "golden" not in spec
+        dD = hip.DeviceArray.from_host(np.asfortranarray(D))
+        dLstar = hip.DeviceArray.from_host(np.asfortranarray(d["Lstar"]))
+        s = tritd.Session(r, opts, A0, B0, C0, n1=n1, n2=n2, n3=n3, i0=i0, i1=i1,
+                          d_device_ptr=dD.ptr + 8 * i0, ldD=n1, device=0, comm=comm, probe=False)
+        dD.free()
+    elif kind == "admm":
         s = tritd.Session(r, opts, A0, B0, C0, n1=n1, n2=n2, n3=n3, i0=i0, i1=i1, D=Dl, device=0,
                           comm=comm, probe=False)
     else:
@@ -87,6 +104,9 @@ def _worker(rank, world, spec, outdir):
     s.run(int(opts["maxIter"]))
     s.sync()
     res = s.get()
+    if dLstar is not None:  # this rank's part of the driver's RRE against L*(i0,0,0), ldX = n1
+        res["num"], res["den"] = s.rre_parts(dLstar.ptr + 8 * i0, n1)
+        dLstar.free()
     s.close()
     comm.close()
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), i0=i0, i1=i1,
@@ -147,6 +167,44 @@ def test_library_schedule_uneven_ranks_match_oracle(tmp_path, world, n1, stop, d
         assert rel(z["B"], rB) < 1e-8 and rel(z["C"], rC) < 1e-8
     A, O, E = _assemble(zs, rA.shape, rO.shape)
     assert rel(A, rA) < 1e-8 and rel(O, rO) < 1e-9 and rel(E, rE) < 1e-9
+
+
+@pytest.mark.timeout(240)
+@pytest.mark.parametrize("world,n1", [(2, 33), (3, 49)])
+def test_ranks_on_the_whole_device_tensor_and_sharded_rre_parts(tmp_path, world, n1):
+    """Every rank creates its session from D(i0,0,0) of the whole device
+    tensor with ldD = n1 (i0 = 17, 33: odd) and calls rre_parts on
+    L*(i0,0,0) with ldX = n1, over the torch-free rendezvous transport (the
+    device-pointer entry points want one HIP runtime in the process).  The
+    solve matches the oracle as above, and the ranks' num and den sum to the
+    float64 restatement on the assembled factors at the tolerances of
+    tests/test_gpu_session_boundary.py (boundary_cases.rre_reference).
+    Measured on an MI355X: both sums equal the restatement to the last bit in
+    either world (num tolerance 3.9e-12 and 1.5e-12)."""
+    import boundary_cases as bc
+    import tritd_oracle as orc
+    d, opts = _case(n1, False)
+    rA, rB, rC, rO, reh, rE, rk, _ = orc.triple_decomp_ADMM(d["D"], 2, opts, d["A0"], d["B0"],
+                                                            d["C0"], printer=lambda s: None)
+    zs = _run(tmp_path, world, dict(kind="admm", n1=n1, stop=False, rdzv=True, full_device=True))
+    assert [int(z["i0"]) for z in zs][1:] == [17, 33][:world - 1]
+    for z in zs:
+        assert int(z["k"]) == rk
+        np.testing.assert_allclose(z["errHist"], reh, rtol=1e-8, atol=1e-13)
+        assert rel(z["B"], rB) < 1e-8 and rel(z["C"], rC) < 1e-8
+        np.testing.assert_array_equal(z["B"], zs[0]["B"])
+        np.testing.assert_array_equal(z["C"], zs[0]["C"])
+    A, O, E = _assemble(zs, rA.shape, rO.shape)
+    assert rel(A, rA) < 1e-8 and rel(O, rO) < 1e-9 and rel(E, rE) < 1e-9
+    L = orc.triple_product(A, zs[0]["B"], zs[0]["C"])
+    num_ref, den_ref, rtol_num, rtol_den = bc.rre_reference(L, d["Lstar"])
+    num, den = sum(float(z["num"]) for z in zs), sum(float(z["den"]) for z in zs)
+    print("  sharded rre_parts world=%d: num %.17g (ref %.17g) dev %.1e of %.1e | den dev %.1e of %.1e"
+          % (world, num, num_ref, abs(num - num_ref) / num_ref, rtol_num,
+             abs(den - den_ref) / den_ref, rtol_den), flush=True)
+    assert all(float(z["num"]) > 0 and float(z["den"]) > 0 for z in zs)
+    assert abs(num - num_ref) <= rtol_num * num_ref
+    assert abs(den - den_ref) <= rtol_den * den_ref
 
 
 @pytest.mark.timeout(240)
