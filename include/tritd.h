@@ -124,6 +124,22 @@ tritd_status tritd_admm_f32(const float* D, int64_t n1, int64_t n2, int64_t n3, 
                             const tritd_opts* opts, const double* A0, const double* B0,
                             const double* C0, double* A, double* B, double* C, float* O, float* E,
                             double* errHist, int32_t* iters, int32_t device);
+/* Mask-aware form (fp64): fit the observed entries only.  `observed` is
+ * n1*n2*n3 bytes laid out like D (host, column-major), nonzero = observed.
+ * Unobserved entries of D are never read as data (any fill value, NaN
+ * included): D <- observed .* D and normD = ||observed .* D|| before the loop
+ * (:28), and in every iteration D~ = where(observed, D, L) stands for D in
+ * :41, :50 and in the next iteration's :33.  O, E and the multipliers are then
+ * exactly 0 at unobserved entries, the factor updates see the current model L
+ * there, and errHist counts observed entries only.  observed == NULL behaves
+ * as tritd_admm_f64; a mask with no true entry is TRITD_ERR_ARG.  device = -1
+ * runs on the device set (mode-1 shards, one device repeated P times
+ * included).  opts.model = TRITD_MODEL_QI is supported. */
+tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int64_t n1, int64_t n2,
+                                   int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
+                                   const double* B0, const double* C0, double* A, double* B,
+                                   double* C, double* O, double* E, double* errHist, int32_t* iters,
+                                   int32_t device);
 
 /* ---------------------------------------------------------------------------
  * Sessions: the device-resident ADMM loop, steppable (bench), shardable
@@ -151,6 +167,21 @@ tritd_status tritd_session_create(tritd_session** out, int32_t device, const voi
                                   int32_t r, const tritd_opts* opts, const double* A0,
                                   const double* B0, const double* C0, tritd_comm* comm,
                                   uint32_t flags);
+/* tritd_session_create with a mask (see tritd_admm_masked_f64).  observed
+ * points at the mask byte of D(i0,0,0); consecutive (j,t) fibres are ldD BYTES
+ * apart (the mask has the shape and leading dimension of D, one byte per
+ * element).  It is a device pointer exactly when TRITD_SESSION_D_ON_DEVICE is
+ * set.  observed == NULL: as tritd_session_create.  With TRITD_SESSION_F32 a
+ * mask is TRITD_ERR_UNSUPPORTED; a mask with no true entry in any shard is
+ * TRITD_ERR_ARG (with a communicator: on every rank alike). */
+tritd_status tritd_session_create_masked(tritd_session** out, int32_t device, const void* D,
+                                         const uint8_t* observed, int64_t ldD, int64_t n1,
+                                         int64_t n2, int64_t n3, int64_t i0, int64_t i1, int32_t r,
+                                         const tritd_opts* opts, const double* A0, const double* B0,
+                                         const double* C0, tritd_comm* comm, uint32_t flags);
+/* Whether the session was created with a mask, and the number of observed
+ * entries of its shard (all of them without a mask).  Either may be NULL. */
+tritd_status tritd_session_mask_info(tritd_session* s, int32_t* masked, int64_t* observed_count);
 /* Enqueue `iters` ADMM iterations (no host synchronisation unless opts.disp).
  * Iterations after the stop test of :63 fires, or beyond maxIter, are no-ops. */
 tritd_status tritd_session_run(tritd_session* s, int32_t iters);

@@ -502,26 +502,29 @@ void run_threaded(DeviceGroup& grp, F&& shard) {
 void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags,
                       int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
                       const double* A0, const double* B0, const double* C0, double* A, double* B,
-                      double* C, void* O, void* E, double* errHist, int32_t* iters);
+                      double* C, void* O, void* E, double* errHist, int32_t* iters,
+                      const uint8_t* observed = nullptr);
 
+// observed (or null): the byte mask of tritd_admm_masked_f64, laid out like D
 void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags, int64_t n1,
                int64_t n2, int64_t n3, int32_t r, const tritd_opts& o, const double* A0,
                const double* B0, const double* C0, double* A, double* B, double* C, void* O,
-               void* E, double* errHist, int32_t* iters) {
+               void* E, double* errHist, int32_t* iters, const uint8_t* observed = nullptr) {
     {
         // TRITD_SHOV=0: the phase-serial order of round 1 (one host thread
         // enqueues every shard's phases, three reductions per iteration)
         const char* sh = std::getenv("TRITD_SHOV");
         if (sh && std::atoi(sh) == 0) {
             run_group_serial(devs, D, es, flags, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
-                             errHist, iters);
+                             errHist, iters, observed);
             return;
         }
     }
     DeviceGroup grp(devs, n1);
     const int P = grp.size();
     if (P == 1) {
-        Session s(devs[0], D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, flags);
+        Session s(devs[0], D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, flags, nullptr,
+                  false, observed);
         OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * es);
         s.run(o.maxIter);
         pf.join();
@@ -534,7 +537,7 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
     run_threaded(grp, [&](int p, tritd_comm* comm) {
         const auto [i0, i1] = grp.rows(p, n1);
         Session s(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3, i0, i1, r, o, A0,
-                  B0, C0, comm, flags);
+                  B0, C0, comm, flags, nullptr, false, observed ? observed + i0 : nullptr);
         s.run(o.maxIter);
         int k = 0;
         s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
@@ -551,7 +554,8 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
 void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags,
                       int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
                       const double* A0, const double* B0, const double* C0, double* A, double* B,
-                      double* C, void* O, void* E, double* errHist, int32_t* iters) {
+                      double* C, void* O, void* E, double* errHist, int32_t* iters,
+                      const uint8_t* observed) {
     DeviceGroup grp(devs, n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<Session>> ss;
@@ -560,7 +564,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new Session(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3,
                                     i0, i1, r, o, A0, B0, C0, nullptr, flags, grp.vst,
-                                    /*defer_normD=*/true));
+                                    /*defer_normD=*/true, observed ? observed + i0 : nullptr));
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
     grp.reduce(ss, &Session::red3, 2);
@@ -745,6 +749,15 @@ tritd_status tritd_admm_f64(const double* D, int64_t n1, int64_t n2, int64_t n3,
                             const tritd_opts* opts, const double* A0, const double* B0,
                             const double* C0, double* A, double* B, double* C, double* O,
                             double* E, double* errHist, int32_t* iters, int32_t device) {
+    return tritd_admm_masked_f64(D, nullptr, n1, n2, n3, r, opts, A0, B0, C0, A, B, C, O, E, errHist,
+                                 iters, device);
+}
+
+tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int64_t n1, int64_t n2,
+                                   int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
+                                   const double* B0, const double* C0, double* A, double* B,
+                                   double* C, double* O, double* E, double* errHist, int32_t* iters,
+                                   int32_t device) {
     std::lock_guard<std::mutex> lk(g_mutex);
     g_last_flags = 0;
     return guarded([&] {
@@ -754,11 +767,12 @@ tritd_status tritd_admm_f64(const double* D, int64_t n1, int64_t n2, int64_t n3,
         const tritd_opts o = normalized(opts);
         if (device < 0 && g_devices.size() > 1) {
             run_group(g_devices, D, sizeof(double), 0, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
-                      errHist, iters);
+                      errHist, iters, observed);
             return;
         }
         const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, 0);
+        Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, 0, nullptr, false,
+                  observed);
         OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * sizeof(double));
         s.run(o.maxIter);
         pf.join();
@@ -814,6 +828,40 @@ tritd_status tritd_session_create(tritd_session** out, int32_t device, const voi
         auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
                               comm, flags);
         *out = reinterpret_cast<tritd_session*>(s);
+    });
+}
+
+tritd_status tritd_session_create_masked(tritd_session** out, int32_t device, const void* D,
+                                         const uint8_t* observed, int64_t ldD, int64_t n1,
+                                         int64_t n2, int64_t n3, int64_t i0, int64_t i1, int32_t r,
+                                         const tritd_opts* opts, const double* A0, const double* B0,
+                                         const double* C0, tritd_comm* comm, uint32_t flags) {
+    return guarded([&] {
+        need(out, "out");
+        *out = nullptr;
+        check_opts(opts);
+        check_dims(n1, n2, n3, r, true);
+        need(D, "D"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
+        if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
+        if (ldD < i1 - i0) throw Error(TRITD_ERR_ARG, "ldD smaller than the shard");
+        // (before any device is touched: a host without a GPU reports it too)
+        if (observed && (flags & TRITD_SESSION_F32))
+            throw Error(TRITD_ERR_UNSUPPORTED, "observed (a mask) is implemented for a double D only");
+        const int dev = pick_device(device);
+        auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
+                              comm, flags, nullptr, false, observed);
+        *out = reinterpret_cast<tritd_session*>(s);
+    });
+}
+
+tritd_status tritd_session_mask_info(tritd_session* s, int32_t* masked, int64_t* observed_count) {
+    return guarded([&] {
+        need(s, "session");
+        int m = 0;
+        int64_t c = 0;
+        reinterpret_cast<Session*>(s)->mask_info(&m, &c);
+        if (masked) *masked = m;
+        if (observed_count) *observed_count = c;
     });
 }
 

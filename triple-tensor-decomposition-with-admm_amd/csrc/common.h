@@ -148,6 +148,12 @@ constexpr int CE_CAP = 27;
 constexpr int CE_IDX_BYTE = 8 * CE_CAP;  // 216
 constexpr int CE_CNT_WORD = 31;
 constexpr int CE_IMG = 256 + 64;
+// Observation mask (MK, opts.observed).  Four 64-bit words per tile, the words
+// of tile ordinal b at M + 4 b (so the tiles are group-major like the tensors):
+// bit l of word w is set when the element lane l holds in register w (in-tile
+// position 64 w + l of the compact-E bytes above) is observed.  Padding rows
+// and padded t are marked observed: they behave as without a mask.
+constexpr int MK_WORDS = 4;
 
 __host__ __device__ inline int64_t tm_tile_base(int64_t g, int64_t tt, int64_t ntt) {
     return ((((g >> 2) * ntt + tt) << 2) + (g & 3)) << 8;

@@ -203,10 +203,17 @@ __device__ __forceinline__ void ce_encode(const double (&En)[4], int lane, doubl
 // encoded or written.  The session switches to it once E has turned dense
 // (video-like data: every tile overflows its slot and the compact form only
 // adds the slot traffic and the decode/encode work; solver.cpp run()).
-template <int RP, bool PRO, bool DE = false>
+// MK (masked form, opts.observed): the tile's four mask words
+// (a.M: bit l of word w = element w of lane l is observed, common.h) come with
+// the tile's prefetch batch, and right after the L chain every element takes
+// d = observed ? D : L.  D - L is then exactly 0 at an unobserved element, so
+// O, E and Y_L stay exactly 0 there and T_next = L: the factor update imputes
+// the missing entry with the current model.  Nothing else in the chain differs.
+template <int RP, bool PRO, bool DE = false, bool MK = false>
 __global__ __launch_bounds__(64 * K5_WAVES) __attribute__((amdgpu_waves_per_eu(RP >= 128 ? 1 : K5_WPE, K5_WPE)))
 void k5_fused(K5Args a) {
     static_assert(!DE || !PRO, "k5_fused: dense-E mode is an update, not the prologue");
+    static_assert(!MK || !PRO, "k5_fused: the prologue needs no mask (D is zeroed where unobserved)");
     if (*a.stop) return;
     // side job: workgroup 0 runs the R x R solve of the next update_A
     // (sweep.h) beside the walk, so no second stream is needed for it
@@ -339,6 +346,7 @@ void k5_fused(K5Args a) {
         double ce;
         d2v edp[2];
         double cep;
+        u2v mk;  // MK: lane l holds mask word l & 3 of the tile
     };
     __shared__ double csm[K5_WAVES][96];
     double* cs = csm[wid];
@@ -378,6 +386,16 @@ void k5_fused(K5Args a) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), r, vlane + 1024 * p,
                                                (int)(tt * 8192), K5_NT_AUX);
     };
+    // mask words: 4 tiles x 32 B per t-tile from the wave's first tile; lane
+    // l loads word l & 3 of its tile (one 32 B piece per wave).  The address
+    // is kept per lane (made opaque: two VGPRs), not as a fifth stream
+    // descriptor: the compact-E form already uses every SGPR, and a
+    // descriptor plus its scalar offset spilled nine of them.
+    const unsigned long long* mkp = nullptr;
+    if constexpr (MK) {
+        mkp = a.M + ((tm_tile_base(tile, 0, ntt) >> 8) << 2) + (lane & 3);
+        asm volatile("" : "+v"(mkp));
+    }
     auto load = [&](int64_t tt, Regs& nx) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
@@ -385,6 +403,12 @@ void k5_fused(K5Args a) {
             nx.x[1][p] = bld(rYL, tt, p);
             if constexpr (PRO) nx.x[PRO ? 2 : 0][p] = bld(rO, tt, p);
         }
+        if constexpr (MK)
+            // (explicitly a global load: behind the opaque pointer the compiler
+            // would emit a flat load, whose completion it cannot count, and
+            // turn every vmcnt wait of the walk into vmcnt(0) — measured
+            // +3.7 % on K5, profiles/masked/)
+            nx.mk = *(const __attribute__((address_space(1))) u2v*)(mkp + tt * 16);
     };
     auto load_dense = [&](int64_t tt, Regs& nx) {
         const int64_t o = (tm_tile_base(tile, tt, ntt) >> 1) + lane;
@@ -500,14 +524,25 @@ void k5_fused(K5Args a) {
             d4 lacc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int s = 0; s < KS; ++s) lacc = mfma4(opL(buf, s), kr[s], lacc);
+            // MK: the tile's mask words, wave-uniform (the lane condition below
+            // is their inverse ballot, as in ce_encode)
+            uint64_t ob[4] = {0, 0, 0, 0};
+            if constexpr (MK) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+                    ob[w] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cx.mk[1], w) << 32) |
+                            (uint32_t)__builtin_amdgcn_readlane((int)cx.mk[0], w);
+            }
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 d2v YLn2;
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int r = 2 * p + q;
-                    const double d = cx.x[0][p][q], yl = cx.x[1][p][q], e = ev[r];
+                    const double dv = cx.x[0][p][q], yl = cx.x[1][p][q], e = ev[r];
                     const double L = lacc[r];
+                    double d = dv;
+                    if constexpr (MK) d = __builtin_amdgcn_inverse_ballot_w64(ob[r]) ? dv : L;
                     // The statements of :41-53 with their multiply-adds fused
                     // and O formed as (R1 + R2)/2 (muL == muO, :16-17,56-57, so
                     // (muL R1 + muO R2)/(muL + muO) is exactly that average);
@@ -598,6 +633,7 @@ void k5_fused(K5Args a) {
     xa.ed[0] = xa.ed[1] = xb.ed[0] = xb.ed[1] = d2v{0.0, 0.0};
     xa.edp[0] = xa.edp[1] = xb.edp[0] = xb.edp[1] = d2v{0.0, 0.0};
     xa.ce = xb.ce = xa.cep = xb.cep = 0.0;
+    if constexpr (MK) xa.mk = xb.mk = u2v{0u, 0u};
     // Prologue, in issue order: the first SD C^ slices (L2), the first tile
     // and slots (HBM), then the Khatri-Rao gather (L2).  vmcnt is in order,
     // so the slices' LDS writes wait for the slices only, and no L2 round
@@ -749,6 +785,10 @@ void launch_k5(const Geom& g, const K5Args& a, bool prologue, hipStream_t st, bo
     case RPV:                                                                              \
         if (prologue)                                                                      \
             hipLaunchKernelGGL((k5_fused<RPV, true>), grid, block, 0, st, b);              \
+        else if (b.M && dense_e && RPV <= 64)                                              \
+            hipLaunchKernelGGL((k5_fused<RPV, false, (RPV <= 64), true>), grid, block, 0, st, b); \
+        else if (b.M)                                                                      \
+            hipLaunchKernelGGL((k5_fused<RPV, false, false, true>), grid, block, 0, st, b); \
         else if (dense_e && RPV <= 64)                                                     \
             hipLaunchKernelGGL((k5_fused<RPV, false, (RPV <= 64)>), grid, block, 0, st, b); \
         else                                                                               \
@@ -842,11 +882,14 @@ void launch_finish(const double* ss, double normD, int k, double tol, double* er
 }
 
 // O_k = (D + (1/muL_{k+1}) Y_L) - T_{k+1}: D, Y_L, O in tile-major order,
-// T in the TX order of the same tile (common.h)
+// T in the TX order of the same tile (common.h).  M (the mask words, or null):
+// O = 0 at an unobserved element, where T holds L and the expression would
+// give -L (k5_fused MK).
 __global__ __launch_bounds__(256) void k_o_fixup(const double* __restrict__ D,
                                                  const double* __restrict__ YL,
                                                  const double* __restrict__ T, double invL_next,
-                                                 double* __restrict__ O, int64_t Np) {
+                                                 double* __restrict__ O, int64_t Np,
+                                                 const unsigned long long* __restrict__ M) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < Np; e += (int64_t)gridDim.x * 256) {
         const int w = (int)(e & 255);
         const int p = w >> 7, l = (w & 127) >> 1, q = w & 1;
@@ -854,15 +897,17 @@ __global__ __launch_bounds__(256) void k_o_fixup(const double* __restrict__ D,
         const int il = l & 15, tl = (l >> 4) + 4 * r;  // element of this TM slot
         const int s = il >> 2, lx = ((il & 3) << 4) | tl;  // its TX slot
         const int64_t tx = (e & ~(int64_t)255) + ((s >> 1) << 7) + (lx << 1) + (s & 1);
-        O[e] = (D[e] + invL_next * YL[e]) - T[tx];
+        const double v = (D[e] + invL_next * YL[e]) - T[tx];
+        const bool obs = !M || ((M[((e >> 8) << 2) + r] >> l) & 1ull);
+        O[e] = obs ? v : 0.0;
     }
 }
 
 void launch_o_fixup(const Geom& g, const double* D, const double* YL, const double* T,
-                    double invL_next, double* O, hipStream_t st) {
+                    double invL_next, double* O, hipStream_t st, const unsigned long long* M) {
     int64_t b = cdiv(g.Ntm, 256);
     if (b > 16384) b = 16384;
-    hipLaunchKernelGGL(k_o_fixup, dim3((unsigned)b), dim3(256), 0, st, D, YL, T, invL_next, O, g.Ntm);
+    hipLaunchKernelGGL(k_o_fixup, dim3((unsigned)b), dim3(256), 0, st, D, YL, T, invL_next, O, g.Ntm, M);
     TRITD_CHECK_LAUNCH();
 }
 

@@ -667,6 +667,46 @@ void launch_to_tm(const Geom& g, const double* src, int64_t ld, double* dst, hip
     TRITD_CHECK_LAUNCH();
 }
 
+// opts.observed -> mask words (common.h: MK), one wave per tile: lane l tests
+// its four elements (register order w: t%16 = (l>>4) + 4w, i%16 = l&15), the
+// ballots are the words; an unobserved element of D (TM position
+// (w>>1)*128 + 2l + (w&1)) is zeroed, so a fill value never enters the solve;
+// the observed entries of the shard itself are counted (one atomic per wave).
+__global__ __launch_bounds__(256) void k_mask_pack(const uint8_t* __restrict__ obs, int64_t ld,
+                                                   int64_t n1l, int64_t n2, int64_t n3,
+                                                   int64_t n1p, int64_t ntt, int64_t ntiles,
+                                                   unsigned long long* __restrict__ M,
+                                                   double* __restrict__ D,
+                                                   unsigned long long* count) {
+    const int l = threadIdx.x & 63;
+    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // tile ordinal
+    if (blk >= ntiles) return;
+    const int64_t q4 = blk >> 2, grp = q4 / ntt, tt = q4 - grp * ntt;
+    const int64_t g = grp * 4 + (blk & 3);
+    const int64_t row = 16 * g + (l & 15);
+    const int64_t j = row / n1p, i = row - j * n1p;
+    int seen = 0;
+#pragma unroll
+    for (int w = 0; w < MK_WORDS; ++w) {
+        const int64_t t = 16 * tt + (l >> 4) + 4 * w;
+        const bool real = i < n1l && j < n2 && t < n3;
+        const bool on = !real || obs[(t * n2 + j) * ld + i] != 0;
+        const unsigned long long word = __ballot(on);
+        seen += __builtin_popcountll(__ballot(real && on));
+        if (l == w) M[blk * MK_WORDS + w] = word;
+        if (!on) D[(blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1)] = 0.0;
+    }
+    if (l == 0 && seen) atomicAdd(count, (unsigned long long)seen);
+}
+
+void launch_mask_pack(const Geom& g, const uint8_t* obs, int64_t ld, unsigned long long* M,
+                      double* D, unsigned long long* count, hipStream_t st) {
+    const int64_t ntiles = g.Ntm / 256;
+    hipLaunchKernelGGL(k_mask_pack, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, st, obs, ld,
+                       g.n1l, g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
+    TRITD_CHECK_LAUNCH();
+}
+
 void launch_from_tm(const Geom& g, const double* src, double* dst, int64_t ld, hipStream_t st) {
     hipLaunchKernelGGL(k_from_tm, dim3(grid_for(g.n1l * g.n2 * g.n3)), dim3(256), 0, st, src,
                        g.n1l, g.n2, g.n3, g.n1p, g.ntt, dst, ld);

@@ -84,6 +84,9 @@ struct K5Args {
     int64_t ahj, bhj;
     SideSolve side;  // RP <= 64, CP model: solve A of the next iteration
     int tsplit = 1;  // chunks of the t-walk (set by launch_k5: k5_tsplit)
+    // mask words of opts.observed (common.h: MK), or null: K5 then runs its
+    // masked instantiation (the prologue never does: D is zeroed where unobserved)
+    const unsigned long long* M = nullptr;
 };
 int k5_grid(const Geom& g);
 // chunks of the fp64 K5's t-walk (1 unless the problem has few ij-tiles); K5
@@ -97,8 +100,10 @@ void launch_k5(const Geom& g, const K5Args& a, bool prologue, hipStream_t st,
 void launch_pool_probe(const Geom& g, double* D, double* YL, double* T, double* CE,
                        hipStream_t st);
 void launch_ce_expand(const Geom& g, const double* CE, double* E, hipStream_t st);
+// (M: the mask words or null; O = 0 at unobserved elements)
 void launch_o_fixup(const Geom& g, const double* D, const double* YL, const double* T,
-                    double invL_next, double* O, hipStream_t st);
+                    double invL_next, double* O, hipStream_t st,
+                    const unsigned long long* M = nullptr);
 // partial sums -> out[0..1] (fixed-order tree)
 void launch_reduce_pairs(const double* partial, int n, double* out, const int* stop, hipStream_t st);
 // both in one launch (single GPU: nothing to all-reduce in between)
@@ -197,6 +202,12 @@ void launch_transpose_batched(const double* in, double* out, int64_t rows, int64
 // n1l x n2 x n3) <-> tile-major (common.h)
 void launch_to_tm(const Geom& g, const double* src, int64_t ld, double* dst, hipStream_t st);
 void launch_from_tm(const Geom& g, const double* src, double* dst, int64_t ld, hipStream_t st);
+// opts.observed: the caller's byte mask (column-major shard like D, fibres ld
+// bytes apart, nonzero = observed) -> mask words M (common.h: MK); the
+// unobserved elements of the tile-major D are zeroed and the observed entries
+// of the shard (pads excluded) added to *count
+void launch_mask_pack(const Geom& g, const uint8_t* obs, int64_t ld, unsigned long long* M,
+                      double* D, unsigned long long* count, hipStream_t st);
 void launch_soft_threshold(const double* X, int64_t n, double lam, double* Y, hipStream_t st);
 void launch_design(char which, const double* P, const double* Q, int64_t nP, int64_t nQ, int r,
                    double* out, hipStream_t st);

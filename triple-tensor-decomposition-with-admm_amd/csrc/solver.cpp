@@ -92,11 +92,13 @@ void unpack_C(const Geom& g, const std::vector<double>& Ch, double* C) {
 Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3,
                  int64_t i0, int64_t i1, int r, const tritd_opts& o, const double* A0,
                  const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
-                 hipStream_t shared_stream, bool defer_normD)
+                 hipStream_t shared_stream, bool defer_normD, const uint8_t* observed)
     : device_(device), o_(o), comm_(comm) {
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
     f32_ = (flags & TRITD_SESSION_F32) != 0;
+    if (observed && f32_)
+        throw Error(TRITD_ERR_UNSUPPORTED, "observed (a mask) is implemented for a double D only");
     probe_ = (flags & TRITD_SESSION_PROBE) != 0;
     es_ = f32_ ? sizeof(float) : sizeof(double);
     // fp32 path and fp64 r = 9..16: padded ranks 16/32/48/64/128/256 (the
@@ -265,6 +267,9 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
             TRITD_HIP(hipStreamSynchronize(st_));
             dstage_.release();
         }
+        // D <- Omega o D and the mask words (fill values, NaN included, never
+        // enter: normD below and T of iteration 1 see the zeroed D)
+        if (observed) pack_mask(observed, ldD, (flags & TRITD_SESSION_D_ON_DEVICE) != 0);
     }
     upload_factors(A0, B0, C0);
 
@@ -275,6 +280,8 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     else
         launch_sumsq_padded(g_, D_.p, sqpart_.p, nb, st_);
     launch_reduce_pairs(sqpart_.p, nb, red3_.p, nullptr, st_);
+    if (masked_)  // the observed count rides beside normD^2 (summed over the shards)
+        TRITD_HIP(hipMemcpyAsync(red3_.p + 1, &obs_count_d_, sizeof(double), hipMemcpyHostToDevice, st_));
     if (!defer_normD) {
         allreduce(red3_.p, 2);
         set_normD_from_red3();
@@ -339,7 +346,39 @@ void Session::set_normD_from_red3() {
     TRITD_HIP(hipMemcpyAsync(ss, red3_.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     normD_ = std::sqrt(ss[0]);
+    if (masked_ && ss[1] == 0.0)
+        throw Error(TRITD_ERR_ARG, "observed has no true entry: nothing to fit");
     if (f32_) normD_ = (double)(float)normD_;  // norm of a single array is single
+}
+
+// opts.observed -> M_ (and D zeroed where unobserved).  A host mask is staged
+// as a contiguous n1l x n2 x n3 byte array first.
+void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device) {
+    masked_ = true;
+    M_.alloc_bytes((size_t)(g_.Ntm / 256) * MK_WORDS * sizeof(unsigned long long));
+    DBuf cnt, stage;
+    cnt.alloc(1);
+    TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
+    const uint8_t* src = observed;
+    int64_t ld = ldD;
+    if (!on_device) {
+        const size_t rows = (size_t)(g_.n2 * g_.n3);
+        stage.alloc_bytes((size_t)g_.n1l * rows);
+        if (ldD == g_.n1l)
+            TRITD_HIP(hipMemcpyAsync(stage.p, observed, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
+        else
+            TRITD_HIP(hipMemcpy2DAsync(stage.p, (size_t)g_.n1l, observed, (size_t)ldD, (size_t)g_.n1l,
+                                       rows, hipMemcpyHostToDevice, st_));
+        src = reinterpret_cast<const uint8_t*>(stage.p);
+        ld = g_.n1l;
+    }
+    launch_mask_pack(g_, src, ld, reinterpret_cast<unsigned long long*>(M_.p), D_.p,
+                     reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    unsigned long long c = 0;
+    TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
+    TRITD_HIP(hipStreamSynchronize(st_));
+    obs_count_ = (int64_t)c;
+    obs_count_d_ = (double)c;
 }
 
 void Session::upload_factors(const double* A0, const double* B0, const double* C0) {
@@ -604,6 +643,7 @@ void Session::launch_k5_any(int k, bool prologue) {
     a.s = scalars(k);
     a.stop = ctrl_;
     a.dense_tiles = dense_tiles();
+    a.M = mask_words();
     if (!prologue) {
         a.side = k5side_;
         k5side_ = SideSolve{};
@@ -1310,7 +1350,7 @@ void Session::get(double* A, double* B, double* C, void* O, void* E, int64_t ldO
             launch_o_fixup32(g_, D_.f(), YL_.f(), T_.f(), (float)(1.0 / mu_[(size_t)done]), O_.f(),
                              st_);
         else
-            launch_o_fixup(g_, D_.p, YL_.p, T_.p, 1.0 / mu_[(size_t)done], O_.p, st_);
+            launch_o_fixup(g_, D_.p, YL_.p, T_.p, 1.0 / mu_[(size_t)done], O_.p, st_, mask_words());
     }
     if (E && g_.n1l > 0) {  // E lives in compact form
         if (f32_)

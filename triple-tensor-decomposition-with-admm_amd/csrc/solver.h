@@ -94,7 +94,7 @@ class Session {
     Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
             int64_t i1, int r, const tritd_opts& o, const double* A0, const double* B0,
             const double* C0, tritd_comm* comm, uint32_t flags, hipStream_t shared_stream = nullptr,
-            bool defer_normD = false);
+            bool defer_normD = false, const uint8_t* observed = nullptr);
     ~Session();
 
     // Enqueue iterations (full collective schedule; used without a virtual group)
@@ -116,6 +116,12 @@ class Session {
         *slot_accesses = de_ ? 0 : (dy_ ? 3 : 2);
     }
     bool dense_e() const { return de_; }
+    // opts.observed: whether the session has a mask, and the observed entries
+    // of its shard
+    void mask_info(int* masked, int64_t* observed_count) const {
+        if (masked) *masked = masked_ ? 1 : 0;
+        if (observed_count) *observed_count = masked_ ? obs_count_ : g_.n1l * g_.n2 * g_.n3;
+    }
     void set_timing(int level);  // 0 off, TRITD_TIMING_ALL, TRITD_TIMING_K5
     void kernel_ms(double* k5, double* m3, double* it, int* samples);
     // per timed iteration (TRITD_TIMING_ALL, with a communicator): ms inside
@@ -227,6 +233,17 @@ class Session {
     DBuf pool_;  // declared first: destroyed after the views into it
     DBuf D_, O_, E_, YL_, YO_, T_, Wk_;
     DBuf CE_;  // compact E slots (common.h)
+    // opts.observed (fp64 only): the mask words (common.h: MK), read by K5's
+    // masked form in every schedule and by the O fix-up; D is stored with its
+    // unobserved entries zeroed, so normD and the prologue need no mask
+    DBuf M_;
+    bool masked_ = false;
+    int64_t obs_count_ = 0;
+    double obs_count_d_ = 0.0;  // (the count as red3_[1]: summed over the shards beside normD^2)
+    const unsigned long long* mask_words() const {
+        return masked_ ? reinterpret_cast<const unsigned long long*>(M_.p) : nullptr;
+    }
+    void pack_mask(const uint8_t* observed, int64_t ldD, bool on_device);
     // derived Y_O (k_admm.hip, fp64 default, TRITD_DY=0 disables): E^(k) lives
     // in compact buffer k % 2 (CE_, CE2_) and dense buffer k % 2 (E_, and the
     // pool slot of Y_O, which is not stored in this mode)

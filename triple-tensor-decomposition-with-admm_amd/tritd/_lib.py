@@ -17,7 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRITD_LIB", os.path.join(HERE, "libtritd.so"))
 
 OK = 0
+TRITD_ERR_ARG = 1
 TRITD_ERR_HIP = 3
+TRITD_ERR_UNSUPPORTED = 7
 STATUS_NAMES = {0: "TRITD_OK", 1: "TRITD_ERR_ARG", 2: "TRITD_ERR_OPTS", 3: "TRITD_ERR_HIP",
                 4: "TRITD_ERR_RCCL", 5: "TRITD_ERR_NOMEM", 6: "TRITD_ERR_NODEV",
                 7: "TRITD_ERR_UNSUPPORTED", 8: "TRITD_ERR_STATE"}
@@ -73,6 +75,12 @@ SIGNATURES = {
                                  vp, vp, vp, C.POINTER(i32), i32]),
     "tritd_admm_f32": (C.c_int, [vp, i64, i64, i64, i32, C.POINTER(Opts), vp, vp, vp, vp, vp, vp,
                                  vp, vp, vp, C.POINTER(i32), i32]),
+    "tritd_admm_masked_f64": (C.c_int, [vp, vp, i64, i64, i64, i32, C.POINTER(Opts), vp, vp, vp, vp,
+                                        vp, vp, vp, vp, vp, C.POINTER(i32), i32]),
+    "tritd_session_create_masked": (C.c_int, [C.POINTER(vp), i32, vp, vp, i64, i64, i64, i64, i64,
+                                              i64, i32, C.POINTER(Opts), vp, vp, vp, vp,
+                                              C.c_uint32]),
+    "tritd_session_mask_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i64)]),
     "tritd_session_create": (C.c_int, [C.POINTER(vp), i32, vp, i64, i64, i64, i64, i64, i64, i32,
                                        C.POINTER(Opts), vp, vp, vp, vp, C.c_uint32]),
     "tritd_session_run": (C.c_int, [vp, i32]),

@@ -92,6 +92,16 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _observed_bytes(observed, shape):
+    """opts.observed -> a column-major uint8 array of D's shape (nonzero =
+    observed); a shape that differs from D's raises like a MATLAB logical
+    index of the wrong size."""
+    m = np.asarray(observed)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"observed must have the shape of D {tuple(shape)}, got {tuple(m.shape)}")
+    return np.asfortranarray(m != 0).view(np.uint8)
+
+
 def initial_factors(n1, n2, n3, r, opts=None, rng=None):
     """A0, B0, C0 in the order of triple_decomp_ADMM.m:23.  Explicit
     opts['A0'/'B0'/'C0'] win (MATLAB's Ziggurat randn is not reproducible
@@ -113,8 +123,14 @@ def initial_factors(n1, n2, n3, r, opts=None, rng=None):
 
 
 def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, return_E=False,
-                       return_iters=False, virtual_shards=0):
+                       return_iters=False, virtual_shards=0, observed=None):
     """[A,B,C,O,errHist] = triple_decomp_ADMM(D, r, opts) on the GPU.
+
+    ``observed`` (a logical array of D's shape, True = observed) fits the
+    observed entries only (tritd_admm_masked_f64): D's values at the other
+    entries are never used (NaN allowed), O and E are exactly 0 there, and
+    errHist counts observed entries only.  float64 D; for mode-1 shards set
+    the device set (``set_devices``), not ``virtual_shards``.
 
     Extra outputs beyond the reference signature: E (``return_E``) and the
     iteration count (``return_iters``).  ``virtual_shards=P`` runs the mode-1
@@ -123,10 +139,18 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     `single` D: O, E float32; A, B, C, errHist float64), r <= 16."""
     o = make_opts(opts)
     if np.asarray(D).dtype == np.float32:
+        if observed is not None:
+            raise TritdError(_lib.TRITD_ERR_UNSUPPORTED,
+                             "observed (a mask) is implemented for a double D only")
         return _admm_f32(D, r, o, opts, A0, B0, C0, device, return_E, return_iters)
     D = _fortran(D)
     n1, n2, n3 = _size3(D)
     r = int(r)
+    obs = None
+    if observed is not None:
+        obs = _observed_bytes(observed, D.shape)
+        if virtual_shards and virtual_shards > 1:
+            raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
     if A0 is None or B0 is None or C0 is None:
         A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
     else:
@@ -144,6 +168,11 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
                                                  _ptr(B0), _ptr(C0), int(virtual_shards), _ptr(A),
                                                  _ptr(B), _ptr(Cf), _ptr(O), _ptr(E),
                                                  _ptr(errHist), C.byref(k), int(device)), "triple_decomp_ADMM")
+    elif obs is not None:
+        check_flags(lib.tritd_admm_masked_f64(_ptr(D), _ptr(obs), n1, n2, n3, r, C.byref(o), _ptr(A0),
+                                              _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(O),
+                                              _ptr(E), _ptr(errHist), C.byref(k), int(device)),
+                    "triple_decomp_ADMM")
     else:
         check_flags(lib.tritd_admm_f64(_ptr(D), n1, n2, n3, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
                                  _ptr(A), _ptr(B), _ptr(Cf), _ptr(O), _ptr(E), _ptr(errHist),
@@ -393,10 +422,15 @@ class Session:
     float32 (or a float32 D) selects the single-class path.  ``probe``
     (default True) times candidate placements of the tensor pool at creation
     and keeps the fastest (TRITD_SESSION_PROBE): worth it for a session that
-    runs hundreds of iterations, not for one solve."""
+    runs hundreds of iterations, not for one solve.
+
+    ``observed`` is the mask of the shard (tritd_session_create_masked): with
+    a host D a logical array of D's shape, with ``d_device_ptr`` a device
+    pointer to bytes laid out like D (fibres ldD bytes apart).  float64 only."""
 
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, D=None,
-                 d_device_ptr=None, ldD=None, device=0, comm=None, dtype=None, probe=True):
+                 d_device_ptr=None, ldD=None, device=0, comm=None, dtype=None, probe=True,
+                 observed=None):
         self._s = C.c_void_p()
         o = make_opts(opts)
         i1 = n1 if i1 is None else i1
@@ -414,15 +448,30 @@ class Session:
             dptr = C.c_void_p(int(d_device_ptr))
             flags |= _lib.SESSION_D_ON_DEVICE
             ldD = ldD if ldD is not None else (i1 - i0)
+            optr = C.c_void_p(int(observed)) if observed is not None else None
         else:
             D = np.asfortranarray(D, dtype=np.float32 if self.f32 else np.float64)
             dptr = _ptr(D)
             ldD = ldD if ldD is not None else D.shape[0]
+            obs = _observed_bytes(observed, D.shape) if observed is not None else None
+            optr = _ptr(obs)
         self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
         self.maxIter = o.maxIter
+        if optr is not None:
+            check(lib.tritd_session_create_masked(C.byref(self._s), int(device), dptr, optr, int(ldD),
+                                                  n1, n2, n3, i0, i1, r, C.byref(o), _ptr(A0),
+                                                  _ptr(B0), _ptr(C0),
+                                                  comm.handle if comm is not None else None, flags))
+            return
         check(lib.tritd_session_create(C.byref(self._s), int(device), dptr, int(ldD), n1, n2, n3,
                                        i0, i1, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
                                        comm.handle if comm is not None else None, flags))
+
+    def mask_info(self):
+        """(whether the session has a mask, observed entries of its shard)"""
+        m, c = _lib.i32(0), _lib.i64(0)
+        check(lib.tritd_session_mask_info(self._s, C.byref(m), C.byref(c)))
+        return bool(m.value), c.value
 
     def run(self, iters):
         check(lib.tritd_session_run(self._s, int(iters)))

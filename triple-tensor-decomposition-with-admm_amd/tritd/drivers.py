@@ -68,10 +68,13 @@ def _observe(X, mask):
 
 
 def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0=None, C0=None,
-                   printer=print, name="data"):
+                   printer=print, name="data", use_mask=False):
     """TRIPLE branch of traffic_triple_comparison.m (:26-64): mask, zero the
     missing entries, solve, `X_hat = triple_product(A,B,C)`, RRE over all
-    entries with `evaluate(X_hat, X, true(size(X)))`, print as at :64."""
+    entries with `evaluate(X_hat, X, true(size(X)))`, print as at :64.
+    `use_mask` (not in the reference, which lets the solver explain the zeros
+    as outliers) tells the solver which entries are missing
+    (`observed = ~mask`): it then fits the observed ones only."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     rng = np.random.default_rng(seed)
     mask = missing_mask(X.shape, missing_ratio, rng)
@@ -79,7 +82,8 @@ def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0
     Y = _observe(X, mask)
     o = dict(TRAFFIC_OPTS if opts is None else opts)
     t0 = time.perf_counter()
-    A, B, C, O, errHist = api.triple_decomp_ADMM(Y, r, o, A0, B0, C0)
+    A, B, C, O, errHist = api.triple_decomp_ADMM(Y, r, o, A0, B0, C0,
+                                                 observed=~mask if use_mask else None)
     timer = time.perf_counter() - t0
     X_hat = api.triple_product(A, B, C)
     rmse, nrmse = api.evaluate(X_hat, X)
@@ -89,14 +93,15 @@ def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0
 
 
 def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=None, C0=None,
-                 printer=print, name="data", save_dir=None):
+                 printer=print, name="data", save_dir=None, use_mask=False):
     """TRIPLE branch of video_triple_comparison.m (:26-76) through the
     `triple_decomp_ADMM_outlier` name the script calls (:54): RMSE/NRMSE of
     X_hat on the missing entries, of O on the observed ones, of X_hat + O on
     all of them, and PSNR/SSIM of X_hat against X (quality_ybz), printed as at
     :74-75.  With `save_dir` the observed tensor is saved as `<name>_raw.mat`
     (variable Y, :32, every ratio) and, when missing_ratio == plot_rate == 0
-    (:58), the errHist / X_hat / O .mat files of :59-61."""
+    (:58), the errHist / X_hat / O .mat files of :59-61.  `use_mask` passes
+    `observed = ~mask` to the solver (see traffic_triple)."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     rng = np.random.default_rng(seed)
     mask = missing_mask(X.shape, missing_ratio, rng)
@@ -109,7 +114,8 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     gt_2 = X.ravel(order="F")[~mask.ravel(order="F")]    # X(~mask_missing)              (:37)
     o = dict(VIDEO_OPTS if opts is None else opts)
     t0 = time.perf_counter()
-    A, B, C, O, errHist = api.triple_decomp_ADMM_outlier(Y, r, o, A0, B0, C0)
+    A, B, C, O, errHist = api.triple_decomp_ADMM_outlier(Y, r, o, A0, B0, C0,
+                                                         **(dict(observed=~mask) if use_mask else {}))
     timer = time.perf_counter() - t0
     X_hat = api.triple_product(A, B, C)
     if save_dir is not None and missing_ratio == 0:
