@@ -305,6 +305,22 @@ tritd_status tritd_als_f64(const double* X, int64_t n1, int64_t n2, int64_t n3, 
                            const tritd_opts* opts, const double* A0, const double* B0,
                            const double* C0, double* A, double* B, double* C, double* errHist,
                            int32_t* iters, int32_t device);
+/* Mask-aware form: fit the observed entries only.  `observed` is n1*n2*n3
+ * bytes laid out like X (host, column-major), nonzero = observed.  Unobserved
+ * entries of X are never read as data (any fill value, NaN and Inf included):
+ * X <- observed .* X and Xnorm = ||observed .* X|| before the loop (:6), and in
+ * iteration k X~ = where(observed, X, Xhat), with Xhat = triple_product(A,B,C)
+ * of :15, stands for X in :16 and in all three updates of that iteration
+ * (:25-38): errHist counts observed entries only and the updates see the
+ * current model at the missing ones.  The stop test, the ridge 1e-9, the
+ * update order and the progress line are unchanged; with every entry observed
+ * every statement is the reference's.  observed == NULL behaves as
+ * tritd_als_f64; a mask with no true entry is TRITD_ERR_ARG.  device = -1 runs
+ * on the device set (mode-1 shards, one device repeated P times included). */
+tritd_status tritd_als_masked_f64(const double* X, const uint8_t* observed, int64_t n1, int64_t n2,
+                                  int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
+                                  const double* B0, const double* C0, double* A, double* B,
+                                  double* C, double* errHist, int32_t* iters, int32_t device);
 /* Steppable ALS session (bench, one process per GPU with comm; shard rows
  * [i0, i1) as for tritd_session_create; flags: TRITD_SESSION_D_ON_DEVICE).
  * quiet = 1 skips the every-5-iterations progress line (and its host
@@ -331,6 +347,23 @@ tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, c
                                       int64_t i1, int32_t r, const tritd_opts* opts,
                                       const double* A0, const double* B0, const double* C0,
                                       tritd_comm* comm, uint32_t flags, int32_t quiet);
+/* tritd_als_session_create with a mask (see tritd_als_masked_f64).  observed
+ * points at the mask byte of X(i0,0,0); consecutive (j,t) fibres are ldX BYTES
+ * apart (the mask has the shape and leading dimension of X, one byte per
+ * element).  It is a device pointer exactly when TRITD_SESSION_D_ON_DEVICE is
+ * set.  observed == NULL: as tritd_als_session_create.  A mask with no true
+ * entry in any shard is TRITD_ERR_ARG (with a communicator: on every rank
+ * alike). */
+tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t device,
+                                             const double* X, const uint8_t* observed, int64_t ldX,
+                                             int64_t n1, int64_t n2, int64_t n3, int64_t i0,
+                                             int64_t i1, int32_t r, const tritd_opts* opts,
+                                             const double* A0, const double* B0, const double* C0,
+                                             tritd_comm* comm, uint32_t flags, int32_t quiet);
+/* Whether the session was created with a mask, and the number of observed
+ * entries of its shard (all of them without a mask).  Either may be NULL. */
+tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
+                                         int64_t* observed_count);
 tritd_status tritd_als_session_run(tritd_als_session* s, int32_t iters);
 tritd_status tritd_als_session_sync(tritd_als_session* s, int32_t* iters_done, int32_t* stopped);
 tritd_status tritd_als_session_get(tritd_als_session* s, double* A, double* B, double* C,

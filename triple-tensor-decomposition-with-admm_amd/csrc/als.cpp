@@ -23,8 +23,21 @@ void emit_line(const char* line);  // api.cpp
 AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int64_t n2,
                        int64_t n3, int64_t i0, int64_t i1, int r, int maxIter, double tol,
                        const double* A0, const double* B0, const double* C0, tritd_comm* comm,
-                       uint32_t flags, hipStream_t shared_stream, bool defer_norm)
+                       uint32_t flags, hipStream_t shared_stream, bool defer_norm,
+                       const uint8_t* observed)
     : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm) {
+    try {  // (a constructor that throws runs no destructor: an all-false mask is refused here)
+        init(X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, flags, shared_stream, defer_norm, observed);
+    } catch (...) {
+        release();
+        throw;
+    }
+}
+
+void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
+                      int64_t i1, int r, const double* A0, const double* B0, const double* C0,
+                      uint32_t flags, hipStream_t shared_stream, bool defer_norm,
+                      const uint8_t* observed) {
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
     if (!rp_supported(g_.RP))
@@ -84,8 +97,13 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
             launch_to_tm(g_, tmp.p, g_.n1l, X_.p, st_);
             TRITD_HIP(hipStreamSynchronize(st_));
         }
+        // X <- Omega o X and the mask words (fill values, NaN included, never
+        // enter: Xnorm below sees the zeroed X)
+        if (observed) pack_mask(observed, ldX, (flags & TRITD_SESSION_D_ON_DEVICE) != 0);
     }
-    launch_tm_to_tx(g_, X_.p, XT_.p, st_);
+    // (a masked session's fit kernel writes the TX copy of the imputed
+    // tensor in every iteration, before K2 reads it)
+    if (!masked_) launch_tm_to_tx(g_, X_.p, XT_.p, st_);
 
     std::vector<double> Ah, AhT, Bh, Ch, ChT;
     pack_A(g_, A0, Ah, AhT);
@@ -101,6 +119,11 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
     const int nb = sumsq_blocks(g_);
     launch_sumsq_padded(g_, X_.p, sqpart_.p, nb, st_);
     launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
+    if (masked_) {  // the observed count rides beside Xnorm^2 (summed over the shards)
+        const double c = (double)obs_count_;
+        TRITD_HIP(hipMemcpyAsync(red0_.p + 1, &c, sizeof(double), hipMemcpyHostToDevice, st_));
+        TRITD_HIP(hipStreamSynchronize(st_));
+    }
     if (!defer_norm) {
         allreduce(red0_.p, 2);
         set_norm_from_red0();
@@ -111,19 +134,55 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
     TRITD_HIP(hipStreamSynchronize(st_));
 }
 
-AlsSession::~AlsSession() {
+void AlsSession::release() {
     hip_quiet(hipSetDevice(device_));
     if (st_) hip_quiet(hipStreamSynchronize(st_));
     for (auto e : ev_) hip_quiet(hipEventDestroy(e));
+    ev_.clear();
     if (ctrl_) hip_quiet(hipFree(ctrl_));
+    ctrl_ = nullptr;
     if (own_stream_ && st_) hip_quiet(hipStreamDestroy(st_));
+    st_ = nullptr;
 }
+
+AlsSession::~AlsSession() { release(); }
 
 void AlsSession::set_norm_from_red0() {
     double ss[2];
     TRITD_HIP(hipMemcpyAsync(ss, red0_.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     Xnorm_ = std::sqrt(ss[0]);
+    if (masked_ && ss[1] == 0.0)
+        throw Error(TRITD_ERR_ARG, "observed has no true entry: nothing to fit");
+}
+
+// observed -> M_ (and X zeroed where unobserved), as Session::pack_mask.  A
+// host mask is staged as a contiguous n1l x n2 x n3 byte array first.
+void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device) {
+    masked_ = true;
+    M_.alloc_bytes((size_t)(g_.Ntm / 256) * MK_WORDS * sizeof(unsigned long long));
+    DBuf cnt, stage;
+    cnt.alloc(1);
+    TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
+    const uint8_t* src = observed;
+    int64_t ld = ldX;
+    if (!on_device) {
+        const size_t rows = (size_t)(g_.n2 * g_.n3);
+        stage.alloc_bytes((size_t)g_.n1l * rows);
+        if (ldX == g_.n1l)
+            TRITD_HIP(hipMemcpyAsync(stage.p, observed, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
+        else
+            TRITD_HIP(hipMemcpy2DAsync(stage.p, (size_t)g_.n1l, observed, (size_t)ldX, (size_t)g_.n1l,
+                                       rows, hipMemcpyHostToDevice, st_));
+        src = reinterpret_cast<const uint8_t*>(stage.p);
+        ld = g_.n1l;
+    }
+    launch_mask_pack(g_, src, ld, reinterpret_cast<unsigned long long*>(M_.p), X_.p,
+                     reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    unsigned long long c = 0;
+    TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
+    TRITD_HIP(hipStreamSynchronize(st_));
+    obs_count_ = (int64_t)c;
 }
 
 void AlsSession::allreduce(double* buf, int64_t count) {
@@ -137,6 +196,8 @@ int AlsSession::next_iter() {
 }
 
 void AlsSession::enable_ncvx(const NcvxParams& p) {
+    if (masked_)
+        throw Error(TRITD_ERR_UNSUPPORTED, "the nonconvex solver has no masked form (observed)");
     TRITD_HIP(hipSetDevice(device_));
     ncvx_ = true;
     np_ = p;
@@ -154,6 +215,10 @@ void AlsSession::phaseFit(int k) {
     a.n1p = g_.n1p; a.n2 = g_.n2; a.n3p = g_.n3p; a.plane = g_.plane; a.tiles = g_.tiles;
     a.ntt = g_.ntt;
     a.stop = ctrl_;
+    if (masked_) {  // X~ = where(Omega, X, Xhat) into XT_ for this iteration's K2
+        a.M = reinterpret_cast<const unsigned long long*>(M_.p);
+        a.XT = XT_.p;
+    }
     if (ncvx_) {  // test.m:35-48; O of iteration k-1 in buffer (k-1)&1, O of k into k&1
         a.ncvx = 1;
         a.O_in = ((k - 1) & 1) ? Ob_.p : Oa_.p;

@@ -18,10 +18,14 @@ class AlsSession {
     // X: double, column-major shard rows [i0, i1) with leading dim ldX (host,
     // or device with TRITD_SESSION_D_ON_DEVICE).  maxIter, tol: the only
     // opts fields the reference reads (triple_decomp_ALS.m:2-3).
+    // observed (or null): the byte mask of the shard, laid out like X (fibres
+    // ldX bytes apart, nonzero = observed; host or device like X).  The
+    // session then fits the observed entries only (tritd_als_masked_f64).
     AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3,
                int64_t i0, int64_t i1, int r, int maxIter, double tol, const double* A0,
                const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
-               hipStream_t shared_stream = nullptr, bool defer_norm = false);
+               hipStream_t shared_stream = nullptr, bool defer_norm = false,
+               const uint8_t* observed = nullptr);
     ~AlsSession();
     AlsSession(const AlsSession&) = delete;
     AlsSession& operator=(const AlsSession&) = delete;
@@ -42,6 +46,12 @@ class AlsSession {
     // errHist/stop/print at the END of the iteration (test.m:62-68).
     void enable_ncvx(const NcvxParams& p);
     bool ncvx() const { return ncvx_; }
+    // whether the session has a mask, and the observed entries of its shard
+    // (all of them without a mask)
+    void mask_info(int* masked, int64_t* observed_count) const {
+        if (masked) *masked = masked_ ? 1 : 0;
+        if (observed_count) *observed_count = masked_ ? obs_count_ : g_.n1l * g_.n2 * g_.n3;
+    }
     // O returned by test.m: that of iteration k-1 when the stop test broke
     // the loop at k (:67 before :71), else the last one; column-major shard
     void get_O(double* O, int64_t ldO);
@@ -90,6 +100,17 @@ class AlsSession {
     bool ncvx_ = false;
     NcvxParams np_{};
     DBuf Oa_, Ob_, Lam_, Gam_;  // ncvx: O double buffer (iteration parity), duals (tile-major)
+    // observed=: the mask words (common.h: MK) read by the masked fit kernel,
+    // which also writes XT_ every iteration; X_ holds Omega o X, so Xnorm
+    // needs no mask.  The observed count rides in red0_[1] at creation.
+    DBuf M_;
+    bool masked_ = false;
+    int64_t obs_count_ = 0;
+    void pack_mask(const uint8_t* observed, int64_t ldX, bool on_device);
+    void init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
+              int64_t i1, int r, const double* A0, const double* B0, const double* C0,
+              uint32_t flags, hipStream_t shared_stream, bool defer_norm, const uint8_t* observed);
+    void release();  // what the destructor frees beyond the members' own
 };
 
 }  // namespace tritd

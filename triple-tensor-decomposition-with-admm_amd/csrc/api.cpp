@@ -600,22 +600,24 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
 void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
                           int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
                           const double* B0, const double* C0, double* A, double* B, double* C,
-                          double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O);
+                          double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O,
+                          const uint8_t* observed);
 
 // triple_decomp_ALS / the test.m solver over a device set: one AlsSession
 // per shard with a communicator (its run() carries the fit-sum, [M2 | A^TA]
 // and M3 all-reduces), one host thread per shard (run_threaded);
 // TRITD_SHOV=0 keeps the phase-serial order (run_als_group_serial).
+// observed (or null): the byte mask of tritd_als_masked_f64, laid out like X.
 void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
                    int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
                    const double* B0, const double* C0, double* A, double* B, double* C,
                    double* errHist, int32_t* iters, const NcvxParams* ncvx = nullptr,
-                   double* O = nullptr) {
+                   double* O = nullptr, const uint8_t* observed = nullptr) {
     {
         const char* sh = std::getenv("TRITD_SHOV");
         if (sh && std::atoi(sh) == 0) {
             run_als_group_serial(devs, X, n1, n2, n3, r, maxIter, tol, A0, B0, C0, A, B, C, errHist,
-                                 iters, ncvx, O);
+                                 iters, ncvx, O, observed);
             return;
         }
     }
@@ -623,7 +625,8 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
     run_threaded(grp, [&](int p, tritd_comm* comm) {
         const auto [i0, i1] = grp.rows(p, n1);
         AlsSession s(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0, B0, C0,
-                     grp.size() > 1 ? comm : nullptr, 0);
+                     grp.size() > 1 ? comm : nullptr, 0, nullptr, false,
+                     observed ? observed + i0 : nullptr);
         if (ncvx) s.enable_ncvx(*ncvx);
         s.run(maxIter);
         int k = 0;
@@ -637,7 +640,8 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
 void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
                           int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
                           const double* B0, const double* C0, double* A, double* B, double* C,
-                          double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O) {
+                          double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O,
+                          const uint8_t* observed) {
     DeviceGroup grp(devs, n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<AlsSession>> ss;
@@ -645,7 +649,8 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         const auto [i0, i1] = grp.rows(p, n1);
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new AlsSession(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0,
-                                       B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true));
+                                       B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true,
+                                       observed ? observed + i0 : nullptr));
         if (ncvx) ss.back()->enable_ncvx(*ncvx);
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
@@ -1110,6 +1115,14 @@ tritd_status tritd_als_f64(const double* X, int64_t n1, int64_t n2, int64_t n3, 
                            const tritd_opts* opts, const double* A0, const double* B0,
                            const double* C0, double* A, double* B, double* C, double* errHist,
                            int32_t* iters, int32_t device) {
+    return tritd_als_masked_f64(X, nullptr, n1, n2, n3, r, opts, A0, B0, C0, A, B, C, errHist,
+                                iters, device);
+}
+
+tritd_status tritd_als_masked_f64(const double* X, const uint8_t* observed, int64_t n1, int64_t n2,
+                                  int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
+                                  const double* B0, const double* C0, double* A, double* B,
+                                  double* C, double* errHist, int32_t* iters, int32_t device) {
     std::lock_guard<std::mutex> lk(g_mutex);
     g_last_flags = 0;
     return guarded([&] {
@@ -1119,11 +1132,12 @@ tritd_status tritd_als_f64(const double* X, int64_t n1, int64_t n2, int64_t n3, 
         const int maxIter = opts->maxIter < 0 ? 0 : opts->maxIter;
         if (device < 0 && g_devices.size() > 1) {
             run_als_group(g_devices, X, n1, n2, n3, r, maxIter, opts->tol, A0, B0, C0, A, B, C,
-                          errHist, iters);
+                          errHist, iters, nullptr, nullptr, observed);
             return;
         }
         const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, maxIter, opts->tol, A0, B0, C0, nullptr, 0);
+        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, maxIter, opts->tol, A0, B0, C0, nullptr, 0,
+                     nullptr, false, observed);
         s.run(maxIter);
         int k = 0;
         s.get(A, B, C, errHist, &k);
@@ -1188,6 +1202,16 @@ tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, c
                                       int64_t i1, int32_t r, const tritd_opts* opts,
                                       const double* A0, const double* B0, const double* C0,
                                       tritd_comm* comm, uint32_t flags, int32_t quiet) {
+    return tritd_als_session_create_masked(out, device, X, nullptr, ldX, n1, n2, n3, i0, i1, r, opts,
+                                           A0, B0, C0, comm, flags, quiet);
+}
+
+tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t device,
+                                             const double* X, const uint8_t* observed, int64_t ldX,
+                                             int64_t n1, int64_t n2, int64_t n3, int64_t i0,
+                                             int64_t i1, int32_t r, const tritd_opts* opts,
+                                             const double* A0, const double* B0, const double* C0,
+                                             tritd_comm* comm, uint32_t flags, int32_t quiet) {
     return guarded([&] {
         need(out, "out");
         *out = nullptr;
@@ -1201,9 +1225,21 @@ tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, c
         const int dev = pick_device(device);
         auto* s = new AlsSession(dev, X, ldX, n1, n2, n3, i0, i1, r,
                                  opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0,
-                                 comm, flags);
+                                 comm, flags, nullptr, false, observed);
         s->set_quiet(quiet != 0);
         *out = reinterpret_cast<tritd_als_session*>(s);
+    });
+}
+
+tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
+                                         int64_t* observed_count) {
+    return guarded([&] {
+        need(s, "session");
+        int m = 0;
+        int64_t c = 0;
+        reinterpret_cast<AlsSession*>(s)->mask_info(&m, &c);
+        if (masked) *masked = m;
+        if (observed_count) *observed_count = c;
     });
 }
 

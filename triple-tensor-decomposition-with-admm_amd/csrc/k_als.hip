@@ -13,12 +13,22 @@
 // walking its t-tiles (X tile-major, common.h), tile tt+1 prefetched while
 // tile tt is computed, L and W on v_mfma_f64_16x16x4_f64 with C^ staged per
 // workgroup in LDS.  Algorithmic traffic N*8 B read + W written.
+//
+// MK (masked form, observed=): the tile's four mask words (a.M:
+// bit l of word w = element w of lane l is observed, common.h) come with the
+// tile's prefetch, and right after the L chain every element takes
+// x = observed ? X : L.  x - L is then exactly 0 at an unobserved element (it
+// adds nothing to the residual), W is formed from x, and x is stored in the TX
+// order into a.XT for this iteration's K2: the imputed tensor changes every
+// iteration, so its TX copy is written in the fit's own pass (+N*8 B written,
+// +32 B per tile read) instead of once per solve.
 #include "kernels.h"
 
 namespace tritd {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2v __attribute__((ext_vector_type(2)));
+typedef unsigned int u2v __attribute__((ext_vector_type(2)));
 
 static constexpr int FIT_WAVES = 4;
 
@@ -29,9 +39,25 @@ __device__ __forceinline__ d4 als_mfma4(double a, double b, d4 c) {
 // sign() of MATLAB without branches: 1, -1, 0 for +-0, NaN for NaN
 __device__ __forceinline__ double nc_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : x); }
 
-template <int RP, bool NCV>
+// One tile's registers: x = X; NCV: e = O, Lam, Gam of the same tile; MK: lane
+// l holds mask word l & 3 of the tile.  (The unmasked forms have no mask
+// member, so they compile as before the mask existed.)
+template <bool NCV, bool MK>
+struct FitRegs {
+    d2v x[2];
+    d2v e[NCV ? 3 : 1][2];
+};
+template <bool NCV>
+struct FitRegs<NCV, true> {
+    d2v x[2];
+    d2v e[NCV ? 3 : 1][2];
+    u2v mk;
+};
+
+template <int RP, bool NCV, bool MK = false>
 __global__ __launch_bounds__(64 * FIT_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_als_fit(AlsFitArgs a) {
+    static_assert(!MK || !NCV, "k_als_fit: the nonconvex chain has no masked form");
     if (*a.stop) return;
     constexpr int KS = RP / 4;    // K-steps of the L MFMA
     constexpr int MT = RP / 16;   // k-tiles of W
@@ -50,6 +76,9 @@ void k_als_fit(AlsFitArgs a) {
 
     __shared__ double sCT[2][RP * SK];   // L operand  C^(t0 + l&15, 4s + l>>4)
     __shared__ double sC[2][16 * LDC];   // W operand  C^(t0 + 4r + l>>4, 16m + l&15)
+    // MK: per-wave 16x16 transpose buffer for the TX copy of x (as K5's for T)
+    __shared__ double tsm[MK ? FIT_WAVES : 1][MK ? 16 * 17 : 1];
+    double* ts = tsm[MK ? wid : 0];
     constexpr int SP = 16 * RP / 2;
     constexpr int NS = (SP + 64 * FIT_WAVES - 1) / (64 * FIT_WAVES);
     d2v sv[NS];
@@ -96,18 +125,22 @@ void k_als_fit(AlsFitArgs a) {
 
     // Two named register sets, the t-walk unrolled by two (a copy cur = next
     // would make the compiler wait for the prefetch at the copy; k_admm.hip).
-    struct Regs {
-        d2v x[2];
-        d2v e[NCV ? 3 : 1][2];  // NCV: O, Lam, Gam of the same tile
-    };
+    using Regs = FitRegs<NCV, MK>;
     const d2v* Oi2 = reinterpret_cast<const d2v*>(a.O_in);
     d2v* Oo2 = reinterpret_cast<d2v*>(a.O_out);
     d2v* L2 = reinterpret_cast<d2v*>(a.Lam);
     d2v* G2 = reinterpret_cast<d2v*>(a.Gam);
+    d2v* XT2 = reinterpret_cast<d2v*>(a.XT);
     auto load = [&](int64_t tt, Regs& nx) {
         const int64_t o = (tm_tile_base(tile, tt, ntt) >> 1) + lane;
         nx.x[0] = X2[o];
         nx.x[1] = X2[o + 64];
+        if constexpr (MK)
+            // one 32 B piece per wave, typed as a global load (a flat load's
+            // completion cannot be counted: every vmcnt wait of the walk
+            // would become vmcnt(0), k_admm.hip)
+            nx.mk = *(const __attribute__((address_space(1))) u2v*)(
+                a.M + ((tm_tile_base(tile, tt, ntt) >> 8) << 2) + (lane & 3));
         if constexpr (NCV) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -131,6 +164,34 @@ void k_als_fit(AlsFitArgs a) {
         double xr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) xr[r] = cx.x[r >> 1][r & 1];
+        // the data of the wide XT stores, held live past the W MFMAs (the
+        // store-keep discipline of k_admm.hip; tests/test_isa_store_war.py)
+        d2v keep[2] = {d2v{0.0, 0.0}, d2v{0.0, 0.0}};
+        if constexpr (MK) {
+            // the tile's mask words, wave-uniform; the lane condition is
+            // their inverse ballot (k5_fused MK)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint64_t ob =
+                    ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cx.mk[1], r) << 32) |
+                    (uint32_t)__builtin_amdgcn_readlane((int)cx.mk[0], r);
+                xr[r] = __builtin_amdgcn_inverse_ballot_w64(ob) ? xr[r] : lacc[r];  // X~ = where(Omega, X, Xhat)
+            }
+            // X~ -> "TX" order (common.h): lane l, slot s holds X~(ij = 4s+(l>>4), t = l&15)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ts[(tg + 4 * r) * 17 + il] = xr[r];
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            const int64_t o = (tm_tile_base(tile, tt, ntt) >> 1) + lane;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                d2v tv;
+                tv[0] = ts[il * 17 + 4 * (2 * p) + tg];
+                tv[1] = ts[il * 17 + 4 * (2 * p + 1) + tg];
+                __builtin_nontemporal_store(tv, XT2 + o + 64 * p);
+                keep[p] = tv;
+            }
+        }
         if constexpr (NCV) {
             // test.m:36,44,47,48,62 in MATLAB's operator order (-ffp-contract=off)
             const int64_t o = (tm_tile_base(tile, tt, ntt) >> 1) + lane;
@@ -170,6 +231,7 @@ void k_als_fit(AlsFitArgs a) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
                 wacc[m] = als_mfma4(cR[(4 * r + tg) * LDC + 16 * m + il], xr[r], wacc[m]);
+        if constexpr (MK) asm volatile("" ::"v"(keep[0]), "v"(keep[1]));
         if (pf) stage_store(buf ^ 1);
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
@@ -180,6 +242,7 @@ void k_als_fit(AlsFitArgs a) {
 #pragma unroll
     for (int q = 0; q < (NCV ? 3 : 1); ++q)
         xa.e[q][0] = xa.e[q][1] = xb.e[q][0] = xb.e[q][1] = d2v{0.0, 0.0};
+    if constexpr (MK) xa.mk = xb.mk = u2v{0u, 0u};
     load(0, xa);
     stage_load(0);
     stage_store(0);
@@ -221,10 +284,14 @@ int als_fit_grid(const Geom& g) { return (int)cdiv(g.tiles, FIT_WAVES); }
 
 void launch_als_fit(const Geom& g, const AlsFitArgs& a, hipStream_t st) {
     const dim3 grid(als_fit_grid(g)), block(64 * FIT_WAVES);
+    if (a.M && (a.ncvx || !a.XT))
+        throw Error(TRITD_ERR_UNSUPPORTED, "the masked ALS fit has no nonconvex form and needs XT");
 #define FIT_CASE(RPV)                                                                  \
     case RPV:                                                                          \
         if (a.ncvx)                                                                    \
             hipLaunchKernelGGL((k_als_fit<RPV, true>), grid, block, 0, st, a);         \
+        else if (a.M)                                                                  \
+            hipLaunchKernelGGL((k_als_fit<RPV, false, true>), grid, block, 0, st, a);  \
         else                                                                           \
             hipLaunchKernelGGL((k_als_fit<RPV, false>), grid, block, 0, st, a);        \
         break;
@@ -287,7 +354,8 @@ void launch_ncvx_shrink(const Geom& g, double* Ah, double* AhT, double gamma, do
 
 // Tile-major -> TX (the B-operand order of K2, common.h), tile by tile:
 // TX slot (s, l) at (s>>1)*128 + 2l + (s&1) holds (i%16 = 4s + l>>4,
-// t%16 = l&15).  One-off per ALS solve (X is fixed).
+// t%16 = l&15).  One-off per unmasked ALS solve (X is fixed; a masked session's
+// fit kernel writes the TX copy of the imputed tensor every iteration).
 __global__ __launch_bounds__(256) void k_tm_to_tx(const double* __restrict__ src,
                                                   double* __restrict__ dst, int64_t Ntm) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < Ntm;

@@ -230,6 +230,11 @@ struct AlsFitArgs {
     const double* O_in;
     double *O_out, *Lam, *Gam;
     double rho, tau, onep;
+    // masked form (observed=; M != null, ncvx == 0): the mask words of
+    // launch_mask_pack (common.h: MK) and the TX copy of X~ = where(Omega, X,
+    // Xhat) the kernel writes for this iteration's K2; X holds Omega o X
+    const unsigned long long* M;
+    double* XT;
 };
 int als_fit_grid(const Geom& g);
 void launch_als_fit(const Geom& g, const AlsFitArgs& a, hipStream_t st);

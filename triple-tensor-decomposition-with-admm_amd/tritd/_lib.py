@@ -110,6 +110,12 @@ SIGNATURES = {
                                 vp, C.POINTER(i32), i32]),
     "tritd_als_session_create": (C.c_int, [C.POINTER(vp), i32, vp, i64, i64, i64, i64, i64, i64,
                                            i32, C.POINTER(Opts), vp, vp, vp, vp, C.c_uint32, i32]),
+    "tritd_als_masked_f64": (C.c_int, [vp, vp, i64, i64, i64, i32, C.POINTER(Opts), vp, vp, vp, vp,
+                                       vp, vp, vp, C.POINTER(i32), i32]),
+    "tritd_als_session_create_masked": (C.c_int, [C.POINTER(vp), i32, vp, vp, i64, i64, i64, i64,
+                                                  i64, i64, i32, C.POINTER(Opts), vp, vp, vp, vp,
+                                                  C.c_uint32, i32]),
+    "tritd_als_session_mask_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i64)]),
     "tritd_als_session_run": (C.c_int, [vp, i32]),
     "tritd_als_session_sync": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "tritd_als_session_get": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(i32)]),

@@ -92,13 +92,13 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
-def _observed_bytes(observed, shape):
+def _observed_bytes(observed, shape, what="D"):
     """opts.observed -> a column-major uint8 array of D's shape (nonzero =
     observed); a shape that differs from D's raises like a MATLAB logical
     index of the wrong size."""
     m = np.asarray(observed)
     if tuple(m.shape) != tuple(shape):
-        raise ValueError(f"observed must have the shape of D {tuple(shape)}, got {tuple(m.shape)}")
+        raise ValueError(f"observed must have the shape of {what} {tuple(shape)}, got {tuple(m.shape)}")
     return np.asfortranarray(m != 0).view(np.uint8)
 
 
@@ -272,9 +272,15 @@ def make_als_opts(opts):
 
 
 def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, return_iters=False,
-                      virtual_shards=0):
+                      virtual_shards=0, observed=None):
     """[A,B,C,errHist] = triple_decomp_ALS(X, r, opts) on the GPU
     (fast_robust_triple_tensor/triple_decomp_ALS.m:1-40).
+
+    ``observed`` (a logical array of X's shape, True = observed) fits the
+    observed entries only (tritd_als_masked_f64): X's values at the other
+    entries are never used (NaN allowed), the updates see the current model
+    there, and errHist counts observed entries only.  For mode-1 shards set
+    the device set (``set_devices``), not ``virtual_shards``.
 
     The initial factors are drawn here in the order of :8-10 unless given
     (MATLAB's randn is not reproducible outside MATLAB).  The progress line of
@@ -285,6 +291,11 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
     X = _fortran(X)
     n1, n2, n3 = _size3(X)
     r = int(r)
+    obs = None
+    if observed is not None:
+        obs = _observed_bytes(observed, X.shape, "X")
+        if virtual_shards and virtual_shards > 1:
+            raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
     if A0 is None or B0 is None or C0 is None:
         A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
     else:
@@ -299,6 +310,11 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
                                                 _ptr(B0), _ptr(C0), int(virtual_shards), _ptr(A),
                                                 _ptr(B), _ptr(Cf), _ptr(errHist), C.byref(k),
                                                 int(device)), "triple_decomp_ALS")
+    elif obs is not None:
+        check_flags(lib.tritd_als_masked_f64(_ptr(X), _ptr(obs), n1, n2, n3, r, C.byref(o), _ptr(A0),
+                                             _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf),
+                                             _ptr(errHist), C.byref(k), int(device)),
+                    "triple_decomp_ALS")
     else:
         check_flags(lib.tritd_als_f64(_ptr(X), n1, n2, n3, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
                                 _ptr(A), _ptr(B), _ptr(Cf), _ptr(errHist), C.byref(k),
@@ -564,10 +580,14 @@ class Session:
 class AlsSession:
     """Steppable device-resident triple_decomp_ALS on one mode-1 shard
     (bench; one process per GPU with ``comm``).  ``quiet`` drops the
-    every-5-iterations progress line and its host synchronisation."""
+    every-5-iterations progress line and its host synchronisation.
+
+    ``observed`` is the mask of the shard (tritd_als_session_create_masked):
+    with a host X a logical array of X's shape, with ``x_device_ptr`` a device
+    pointer to bytes laid out like X (fibres ldX bytes apart)."""
 
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, X=None,
-                 x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True):
+                 x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True, observed=None):
         self._s = C.c_void_p()
         o = make_als_opts(opts)
         i1 = n1 if i1 is None else i1
@@ -577,16 +597,32 @@ class AlsSession:
             xptr = C.c_void_p(int(x_device_ptr))
             flags |= _lib.SESSION_D_ON_DEVICE
             ldX = ldX if ldX is not None else (i1 - i0)
+            optr = C.c_void_p(int(observed)) if observed is not None else None
         else:
             X = _fortran(X)
             xptr = _ptr(X)
             ldX = ldX if ldX is not None else X.shape[0]
+            obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
+            optr = _ptr(obs)
         self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
         self.maxIter = o.maxIter
+        if optr is not None:
+            check(lib.tritd_als_session_create_masked(C.byref(self._s), int(device), xptr, optr,
+                                                      int(ldX), n1, n2, n3, i0, i1, r, C.byref(o),
+                                                      _ptr(A0), _ptr(B0), _ptr(C0),
+                                                      comm.handle if comm is not None else None,
+                                                      flags, int(bool(quiet))))
+            return
         check(lib.tritd_als_session_create(C.byref(self._s), int(device), xptr, int(ldX), n1, n2,
                                            n3, i0, i1, r, C.byref(o), _ptr(A0), _ptr(B0),
                                            _ptr(C0), comm.handle if comm is not None else None,
                                            flags, int(bool(quiet))))
+
+    def mask_info(self):
+        """(whether the session has a mask, observed entries of its shard)"""
+        m, c = _lib.i32(0), _lib.i64(0)
+        check(lib.tritd_als_session_mask_info(self._s, C.byref(m), C.byref(c)))
+        return bool(m.value), c.value
 
     def run(self, iters):
         check(lib.tritd_als_session_run(self._s, int(iters)))
