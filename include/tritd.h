@@ -340,6 +340,36 @@ tritd_status tritd_ncvx_f64(const double* X, int64_t n1, int64_t n2, int64_t n3,
                            double theta, int32_t maxIter, double tol, const double* A0,
                            const double* B0, const double* C0, double* A, double* B, double* C,
                            double* O, double* errHist, int32_t* iters, int32_t device);
+/* Mask-aware form of tritd_ncvx_f64: fit the observed entries only.  `observed`
+ * is n1*n2*n3 bytes laid out like X (host, column-major), nonzero = observed
+ * (Omega below).  Line numbers are fast_robust_triple_tensor/test.m's.
+ *   Before the loop X <- Omega .* X and Xnorm = ||Omega .* X|| (:21): the
+ *   values of X at unobserved entries (0, NaN, +-Inf, sentinels) are never read
+ *   as data.  In iteration k, after T = triple_product(A,B,C) (:35),
+ *   X~ = where(Omega, X, T) stands for X.
+ *   At an observed entry :36 (Y_new), :44 (O_new), :47 (Lambda), :48 (Gamma) and
+ *   :62 (errHist) are the reference's statements in the reference's operator
+ *   order.  At an unobserved entry their exact-arithmetic values for x = T,
+ *   O = Lambda = Gamma = 0 are imposed, not computed ((T + rho T)/(1 + rho)
+ *   rounds to something other than T): Y_new = T, O_new = 0, Lambda and Gamma
+ *   keep their value (exactly 0 for every k), and the entry adds exactly 0 to
+ *   errHist(k).  The returned O is exactly 0 where unobserved.
+ *   The factor updates :49-51 (ridge 1e-12 + reweighted shrink on A, 1e-9 on B
+ *   and C) take X~ for X, with T of the start of the iteration: an EM step per
+ *   iteration, as tritd_als_masked_f64.
+ *   Unchanged: the stop test :65-68, errHist = errHist(1:k), the returned O being
+ *   that of iteration k-1 on a break (:71), the progress line of every iteration
+ *   (:63).  With every entry observed the result is that of tritd_ncvx_f64 bit
+ *   for bit; observed == NULL behaves as tritd_ncvx_f64; a mask with no true
+ *   entry is TRITD_ERR_ARG.  device = -1 runs on the device set (mode-1 shards,
+ *   one device repeated P times included; TRITD_SHOV=0: the phase-serial
+ *   order). */
+tritd_status tritd_ncvx_masked_f64(const double* X, const uint8_t* observed, int64_t n1, int64_t n2,
+                                   int64_t n3, int32_t r, double rho, double lambda, double gamma_A,
+                                   double epsilon, double p, double theta, int32_t maxIter,
+                                   double tol, const double* A0, const double* B0, const double* C0,
+                                   double* A, double* B, double* C, double* O, double* errHist,
+                                   int32_t* iters, int32_t device);
 
 typedef struct tritd_als_session tritd_als_session;
 tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, const double* X,
@@ -364,6 +394,22 @@ tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t de
  * entries of its shard (all of them without a mask).  Either may be NULL. */
 tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
                                          int64_t* observed_count);
+/* Turn an ALS session, masked or not, into the nonconvex solver of
+ * fast_robust_triple_tensor/test.m:1-73 (the positional parameters of :1): the
+ * outlier chain :36-48 fused into the fit, ridge 1e-12 + reweighted shrink on A
+ * (:49, :77-92), errHist / stop / progress line at the end of the iteration
+ * (:62-68; the line is printed every iteration unless the session is quiet).  On
+ * a masked session the semantics are those of tritd_ncvx_masked_f64.  Must come
+ * before the first tritd_als_session_run (else, or a second time,
+ * TRITD_ERR_STATE); rho == 0 is TRITD_ERR_ARG. */
+tritd_status tritd_als_session_set_ncvx(tritd_als_session* s, double rho, double lambda,
+                                        double gamma_A, double epsilon, double p, double theta);
+/* O of the session's shard (host, column-major, rows [i0, i1), leading
+ * dimension ldO >= i1 - i0): that of iteration k-1 when the stop test broke the
+ * loop at k (test.m:67 comes before O = O_new, :71), else that of the last
+ * iteration run; exactly 0 where unobserved.  Synchronises.  TRITD_ERR_STATE on
+ * a session without tritd_als_session_set_ncvx. */
+tritd_status tritd_als_session_get_O(tritd_als_session* s, double* O, int64_t ldO);
 tritd_status tritd_als_session_run(tritd_als_session* s, int32_t iters);
 tritd_status tritd_als_session_sync(tritd_als_session* s, int32_t* iters_done, int32_t* stopped);
 tritd_status tritd_als_session_get(tritd_als_session* s, double* A, double* B, double* C,

@@ -196,8 +196,11 @@ int AlsSession::next_iter() {
 }
 
 void AlsSession::enable_ncvx(const NcvxParams& p) {
-    if (masked_)
-        throw Error(TRITD_ERR_UNSUPPORTED, "the nonconvex solver has no masked form (observed)");
+    if (k_enq_ > 0 || ncvx_)
+        throw Error(TRITD_ERR_STATE, "the nonconvex solver is chosen once, before the first run");
+    if (!(p.rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+    // (a masked session: the fit kernel runs the outlier chain on
+    // X~ = where(Omega, X, T) and writes XT_ every iteration, as the masked ALS)
     TRITD_HIP(hipSetDevice(device_));
     ncvx_ = true;
     np_ = p;

@@ -44,6 +44,10 @@ class AlsSession {
     // same fit/M1/M2/K2 kernels over X, plus the O / Lambda / Gamma ADMM
     // chain fused into the fit kernel, ridge 1e-12 + reweighted shrink on A,
     // errHist/stop/print at the END of the iteration (test.m:62-68).
+    // After the first run (or a second time) it throws TRITD_ERR_STATE; rho = 0
+    // is TRITD_ERR_ARG.  On a masked session the chain runs on
+    // X~ = where(Omega, X, T): at an unobserved entry Y_new = T, O_new = 0,
+    // Lambda and Gamma stay 0 and errHist gets nothing (tritd_ncvx_masked_f64).
     void enable_ncvx(const NcvxParams& p);
     bool ncvx() const { return ncvx_; }
     // whether the session has a mask, and the observed entries of its shard

@@ -1171,6 +1171,16 @@ tritd_status tritd_ncvx_f64(const double* X, int64_t n1, int64_t n2, int64_t n3,
                            double theta, int32_t maxIter, double tol, const double* A0,
                            const double* B0, const double* C0, double* A, double* B, double* C,
                            double* O, double* errHist, int32_t* iters, int32_t device) {
+    return tritd_ncvx_masked_f64(X, nullptr, n1, n2, n3, r, rho, lambda, gamma_A, epsilon, p, theta,
+                                 maxIter, tol, A0, B0, C0, A, B, C, O, errHist, iters, device);
+}
+
+tritd_status tritd_ncvx_masked_f64(const double* X, const uint8_t* observed, int64_t n1, int64_t n2,
+                                   int64_t n3, int32_t r, double rho, double lambda, double gamma_A,
+                                   double epsilon, double p, double theta, int32_t maxIter,
+                                   double tol, const double* A0, const double* B0, const double* C0,
+                                   double* A, double* B, double* C, double* O, double* errHist,
+                                   int32_t* iters, int32_t device) {
     std::lock_guard<std::mutex> lk(g_mutex);
     g_last_flags = 0;
     return guarded([&] {
@@ -1182,11 +1192,12 @@ tritd_status tritd_ncvx_f64(const double* X, int64_t n1, int64_t n2, int64_t n3,
         const int mi = maxIter < 0 ? 0 : maxIter;
         if (device < 0 && g_devices.size() > 1) {
             run_als_group(g_devices, X, n1, n2, n3, r, mi, tol, A0, B0, C0, A, B, C, errHist, iters,
-                          &np, O);
+                          &np, O, observed);
             return;
         }
         const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, mi, tol, A0, B0, C0, nullptr, 0);
+        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, mi, tol, A0, B0, C0, nullptr, 0, nullptr,
+                     false, observed);
         s.enable_ncvx(np);
         s.run(mi);
         int k = 0;
@@ -1240,6 +1251,25 @@ tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
         reinterpret_cast<AlsSession*>(s)->mask_info(&m, &c);
         if (masked) *masked = m;
         if (observed_count) *observed_count = c;
+    });
+}
+
+tritd_status tritd_als_session_set_ncvx(tritd_als_session* s, double rho, double lambda,
+                                        double gamma_A, double epsilon, double p, double theta) {
+    return guarded([&] {
+        need(s, "session");
+        reinterpret_cast<AlsSession*>(s)->enable_ncvx(NcvxParams{rho, lambda, gamma_A, epsilon, p, theta});
+    });
+}
+
+tritd_status tritd_als_session_get_O(tritd_als_session* s, double* O, int64_t ldO) {
+    return guarded([&] {
+        need(s, "session");
+        need(O, "O");
+        auto* as = reinterpret_cast<AlsSession*>(s);
+        if (!as->ncvx()) throw Error(TRITD_ERR_STATE, "get_O: not a nonconvex (test.m) session");
+        if (ldO < as->geom().n1l) throw Error(TRITD_ERR_ARG, "ldO smaller than the shard");
+        as->get_O(O, ldO);
     });
 }
 

@@ -22,6 +22,14 @@
 // order into a.XT for this iteration's K2: the imputed tensor changes every
 // iteration, so its TX copy is written in the fit's own pass (+N*8 B written,
 // +32 B per tile read) instead of once per solve.
+//
+// NCV (the nonconvex solver of fast_robust_triple_tensor/test.m:1-73) fuses the
+// outlier chain :36-48 and the residual of :62 into the same pass.  NCV and MK
+// together: the chain runs on x = X~, so W and the TX copy are
+// those of the masked ALS, and at an unobserved element the exact-arithmetic
+// values of the chain for x = L, O = Lambda = Gamma = 0 are imposed per element
+// (O_new = 0, an increment of exactly 0 to Lambda and Gamma, a residual of
+// exactly 0) instead of being left to the rounding of (L + rho L)/(1 + rho).
 #include "kernels.h"
 
 namespace tritd {
@@ -57,7 +65,6 @@ struct FitRegs<NCV, true> {
 template <int RP, bool NCV, bool MK = false>
 __global__ __launch_bounds__(64 * FIT_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_als_fit(AlsFitArgs a) {
-    static_assert(!MK || !NCV, "k_als_fit: the nonconvex chain has no masked form");
     if (*a.stop) return;
     constexpr int KS = RP / 4;    // K-steps of the L MFMA
     constexpr int MT = RP / 16;   // k-tiles of W
@@ -167,15 +174,17 @@ void k_als_fit(AlsFitArgs a) {
         // the data of the wide XT stores, held live past the W MFMAs (the
         // store-keep discipline of k_admm.hip; tests/test_isa_store_war.py)
         d2v keep[2] = {d2v{0.0, 0.0}, d2v{0.0, 0.0}};
+        bool ob[4] = {true, true, true, true};  // MK: element r of this lane is observed
         if constexpr (MK) {
             // the tile's mask words, wave-uniform; the lane condition is
             // their inverse ballot (k5_fused MK)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const uint64_t ob =
+                const uint64_t ow =
                     ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cx.mk[1], r) << 32) |
                     (uint32_t)__builtin_amdgcn_readlane((int)cx.mk[0], r);
-                xr[r] = __builtin_amdgcn_inverse_ballot_w64(ob) ? xr[r] : lacc[r];  // X~ = where(Omega, X, Xhat)
+                ob[r] = __builtin_amdgcn_inverse_ballot_w64(ow);
+                xr[r] = ob[r] ? xr[r] : lacc[r];  // X~ = where(Omega, X, Xhat)
             }
             // X~ -> "TX" order (common.h): lane l, slot s holds X~(ij = 4s+(l>>4), t = l&15)
 #pragma unroll
@@ -193,7 +202,11 @@ void k_als_fit(AlsFitArgs a) {
             }
         }
         if constexpr (NCV) {
-            // test.m:36,44,47,48,62 in MATLAB's operator order (-ffp-contract=off)
+            // test.m:36,44,47,48,62 in MATLAB's operator order (-ffp-contract=off).
+            // MK: at an unobserved element x = L, and the exact-arithmetic
+            // values of these statements there (Y_new = L, O_new = 0, Lambda
+            // and Gamma unchanged, no residual) are imposed, not left to the
+            // rounding of (L + rho L)/(1 + rho)
             const int64_t o = (tm_tile_base(tile, tt, ntt) >> 1) + lane;
             d2v on[2], ln[2], gn[2];
 #pragma unroll
@@ -204,10 +217,12 @@ void k_als_fit(AlsFitArgs a) {
                 const double Y = ((x - O) + a.rho * (L + Lm / a.rho)) / a.onep;
                 const double xy = x - Y;
                 const double z = xy + Gm / a.rho;
-                const double On = nc_sign(z) * fmax(fabs(z) - a.tau, 0.0);
-                const double d = xy - On;
+                const double On = MK ? (ob[r] ? nc_sign(z) * fmax(fabs(z) - a.tau, 0.0) : 0.0)
+                                     : nc_sign(z) * fmax(fabs(z) - a.tau, 0.0);
+                const double d = MK ? (ob[r] ? xy - On : 0.0) : xy - On;
+                const double dl = MK ? (ob[r] ? L - Y : 0.0) : L - Y;
                 on[r >> 1][r & 1] = On;
-                ln[r >> 1][r & 1] = Lm + a.rho * (L - Y);
+                ln[r >> 1][r & 1] = Lm + a.rho * dl;
                 gn[r >> 1][r & 1] = Gm + a.rho * d;
                 ss += d * d;
             }
@@ -284,11 +299,12 @@ int als_fit_grid(const Geom& g) { return (int)cdiv(g.tiles, FIT_WAVES); }
 
 void launch_als_fit(const Geom& g, const AlsFitArgs& a, hipStream_t st) {
     const dim3 grid(als_fit_grid(g)), block(64 * FIT_WAVES);
-    if (a.M && (a.ncvx || !a.XT))
-        throw Error(TRITD_ERR_UNSUPPORTED, "the masked ALS fit has no nonconvex form and needs XT");
+    if (a.M && !a.XT) throw Error(TRITD_ERR_UNSUPPORTED, "the masked ALS fit needs XT");
 #define FIT_CASE(RPV)                                                                  \
     case RPV:                                                                          \
-        if (a.ncvx)                                                                    \
+        if (a.ncvx && a.M)                                                             \
+            hipLaunchKernelGGL((k_als_fit<RPV, true, true>), grid, block, 0, st, a);   \
+        else if (a.ncvx)                                                               \
             hipLaunchKernelGGL((k_als_fit<RPV, true>), grid, block, 0, st, a);         \
         else if (a.M)                                                                  \
             hipLaunchKernelGGL((k_als_fit<RPV, false, true>), grid, block, 0, st, a);  \

@@ -20,6 +20,7 @@ OK = 0
 TRITD_ERR_ARG = 1
 TRITD_ERR_HIP = 3
 TRITD_ERR_UNSUPPORTED = 7
+TRITD_ERR_STATE = 8
 STATUS_NAMES = {0: "TRITD_OK", 1: "TRITD_ERR_ARG", 2: "TRITD_ERR_OPTS", 3: "TRITD_ERR_HIP",
                 4: "TRITD_ERR_RCCL", 5: "TRITD_ERR_NOMEM", 6: "TRITD_ERR_NODEV",
                 7: "TRITD_ERR_UNSUPPORTED", 8: "TRITD_ERR_STATE"}
@@ -138,7 +139,18 @@ SIGNATURES = {
     "tritd_triple_product_qi_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, vp]),
     "tritd_ncvx_f64": (C.c_int, [vp, i64, i64, i64, i32] + [C.c_double] * 6
                        + [i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), i32]),
+    "tritd_ncvx_masked_f64": (C.c_int, [vp, vp, i64, i64, i64, i32] + [C.c_double] * 6
+                              + [i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32),
+                                 i32]),
+    "tritd_als_session_set_ncvx": (C.c_int, [vp] + [C.c_double] * 6),
     "tritd_dev_triple_product_qi_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, vp, vp]),
+}
+
+# Entry points whose name carries a MATLAB variable's capital letter.  Bound
+# exactly like SIGNATURES; kept apart because SIGNATURES is compared with a
+# scan of the header for lower-case names (tests/test_abi.py).
+SIGNATURES_MIXED_CASE = {
+    "tritd_als_session_get_O": (C.c_int, [vp, vp, i64]),
 }
 
 
@@ -222,7 +234,7 @@ def _load():
         raise ImportError(f"libtritd.so not found at {LIB_PATH}: run __graft_entry__.build() "
                           "(or `make` in triple-tensor-decomposition-with-admm_amd/csrc)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **SIGNATURES_MIXED_CASE}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -214,7 +214,7 @@ def _admm_f32(D, r, o, opts, A0, B0, C0, device, return_E, return_iters):
 
 # the name video_triple_comparison.m:54 calls (unresolvable in the reference)
 def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol, A0=None,
-                       B0=None, C0=None, *, device=-1, return_iters=False):
+                       B0=None, C0=None, *, device=-1, return_iters=False, observed=None):
     """[A,B,C,O,errHist] of fast_robust_triple_tensor/test.m:1-73 on the GPU
     (the nonconvex variant): outlier ADMM over
     Y = X - O with duals Lambda/Gamma fused into the ALS fit kernel, the
@@ -222,11 +222,20 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
     sign(A1).*max(|A1| - gamma_A./(|A1|+epsilon).^(theta-p), 0) on A (:77-92).
     The progress line of :63 goes to the printer every iteration.  On the stop
     test (:65-67) errHist is truncated and O is that of the previous iteration
-    (the reference breaks before O = O_new, :71).  fp64, r <= 8."""
+    (the reference breaks before O = O_new, :71).  fp64, r <= 8.
+
+    ``observed`` (a logical array of X's shape, True = observed) fits the
+    observed entries only (tritd_ncvx_masked_f64): X's values at the other
+    entries are never used (NaN allowed); there the chain sees the current
+    model T, so Y = T, O is exactly 0, the duals stay 0 and errHist counts
+    observed entries only, and the factor updates take where(observed, X, T)
+    for X.  With every entry observed the result is the unmasked one, bit for
+    bit.  For mode-1 shards set the device set (``set_devices``)."""
     X = _fortran(X)
     n1, n2, n3 = _size3(X)
     r = int(r)
     maxIter = int(maxIter)
+    obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
     if A0 is None or B0 is None or C0 is None:
         A0, B0, C0 = initial_factors(n1, n2, n3, r)
     else:
@@ -237,10 +246,14 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
     O = np.zeros((n1, n2, n3), order="F")
     errHist = np.zeros(max(maxIter, 1))
     k = _lib.i32(0)
-    check_flags(lib.tritd_ncvx_f64(_ptr(X), n1, n2, n3, r, float(rho), float(lam), float(gamma_A),
-                             float(epsilon), float(p), float(theta), maxIter, float(tol), _ptr(A0),
-                             _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(O), _ptr(errHist),
-                             C.byref(k), int(device)), "triple_decomp_ADMM_outlier")
+    prm = (float(rho), float(lam), float(gamma_A), float(epsilon), float(p), float(theta), maxIter,
+           float(tol), _ptr(A0), _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(O),
+           _ptr(errHist), C.byref(k), int(device))
+    if obs is not None:
+        check_flags(lib.tritd_ncvx_masked_f64(_ptr(X), _ptr(obs), n1, n2, n3, r, *prm),
+                    "triple_decomp_ADMM_outlier")
+    else:
+        check_flags(lib.tritd_ncvx_f64(_ptr(X), n1, n2, n3, r, *prm), "triple_decomp_ADMM_outlier")
     out = [A, B, Cf, O, errHist[: k.value].copy()]
     if return_iters:
         out.append(k.value)
@@ -584,11 +597,20 @@ class AlsSession:
 
     ``observed`` is the mask of the shard (tritd_als_session_create_masked):
     with a host X a logical array of X's shape, with ``x_device_ptr`` a device
-    pointer to bytes laid out like X (fibres ldX bytes apart)."""
+    pointer to bytes laid out like X (fibres ldX bytes apart).
+
+    ``ncvx=dict(rho=, lam=, gamma_A=, epsilon=, p=, theta=)`` turns the session,
+    masked or not, into the nonconvex solver of test.m:1-73
+    (tritd_als_session_set_ncvx; ``triple_decomp_ncvx`` stepped): ``get_O``
+    then returns the shard's O, and with ``quiet=False`` the progress line
+    comes every iteration."""
 
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, X=None,
-                 x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True, observed=None):
+                 x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True, observed=None,
+                 ncvx=None):
         self._s = C.c_void_p()
+        if ncvx is not None:
+            ncvx = [float(ncvx[k]) for k in ("rho", "lam", "gamma_A", "epsilon", "p", "theta")]
         o = make_als_opts(opts)
         i1 = n1 if i1 is None else i1
         A0, B0, C0 = _fortran(A0), _fortran(B0), _fortran(C0)
@@ -612,11 +634,26 @@ class AlsSession:
                                                       _ptr(A0), _ptr(B0), _ptr(C0),
                                                       comm.handle if comm is not None else None,
                                                       flags, int(bool(quiet))))
-            return
-        check(lib.tritd_als_session_create(C.byref(self._s), int(device), xptr, int(ldX), n1, n2,
-                                           n3, i0, i1, r, C.byref(o), _ptr(A0), _ptr(B0),
-                                           _ptr(C0), comm.handle if comm is not None else None,
-                                           flags, int(bool(quiet))))
+        else:
+            check(lib.tritd_als_session_create(C.byref(self._s), int(device), xptr, int(ldX), n1,
+                                               n2, n3, i0, i1, r, C.byref(o), _ptr(A0), _ptr(B0),
+                                               _ptr(C0), comm.handle if comm is not None else None,
+                                               flags, int(bool(quiet))))
+        if ncvx is not None:
+            self.set_ncvx(*ncvx)
+
+    def set_ncvx(self, rho, lam, gamma_A, epsilon, p, theta):
+        """tritd_als_session_set_ncvx: before the first ``run``."""
+        check(lib.tritd_als_session_set_ncvx(self._s, float(rho), float(lam), float(gamma_A),
+                                             float(epsilon), float(p), float(theta)))
+
+    def get_O(self):
+        """O of the shard (rows i0..i1-1), tritd_als_session_get_O: that of
+        iteration k-1 when the stop test broke the loop at k, else the last;
+        exactly 0 where unobserved."""
+        O = np.zeros((self.i1 - self.i0, self.n2, self.n3), order="F")
+        check(lib.tritd_als_session_get_O(self._s, _ptr(O), self.i1 - self.i0))
+        return O
 
     def mask_info(self):
         """(whether the session has a mask, observed entries of its shard)"""
