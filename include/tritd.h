@@ -321,6 +321,42 @@ tritd_status tritd_als_masked_f64(const double* X, const uint8_t* observed, int6
                                   int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
                                   const double* B0, const double* C0, double* A, double* B,
                                   double* C, double* errHist, int32_t* iters, int32_t device);
+/* Held-out validation error and early stopping for the masked ALS.
+ * `observed` (Omega; NULL = all true) and `holdout` (H) are n1*n2*n3 bytes laid
+ * out like X, nonzero = true; patience >= 0.  Only H & Omega counts: a held-out
+ * flag at an unobserved entry is ignored, whatever X holds there (NaN
+ * included).  Line numbers are fast_robust_triple_tensor/triple_decomp_ALS.m's.
+ *   The fit is exactly tritd_als_masked_f64 with observed = Omega & ~H:
+ *   Xnorm = ||(Omega & ~H) .* X|| (:6) and X~ = where(Omega & ~H, X, Xhat)
+ *   stands for X in :16 and :25-38.  With patience = 0, A, B, C, errHist and
+ *   *iters are bit for bit those of that call.
+ *   valHist(k) = ||H .* Omega .* (X - Xhat)|| / ||H .* Omega .* X|| with the Xhat
+ *   of :15 in iteration k: like errHist(k) it scores the factors iteration k
+ *   started with, and it is truncated with errHist (:21).  It is summed in the
+ *   fit kernel's own pass over X.
+ *   best_iter = argmin_k valHist(k), the first minimum on a tie (a strict <
+ *   against the running best, k = 1 always taken).  A_best, B_best, C_best are
+ *   the factors iteration best_iter started with (best_iter = 1: A0, B0, C0
+ *   exactly), kept on the device.
+ *   Early stop, patience = p > 0 only: after the stop test of :20, if
+ *   k - best_iter >= p the loop stops at k like a reference stop: the updates
+ *   of k do not run and A, B, C are the factors of iteration k un-updated.
+ *   stop_reason: 0 ran to maxIter (or not stopped yet), 1 the test of :20,
+ *   2 patience.
+ *   TRITD_ERR_ARG: H & Omega empty, Omega & ~H empty, ||H .* Omega .* X|| = 0,
+ *   patience < 0, holdout == NULL.  On a device set or with a communicator
+ *   every shard refuses alike (the counts and norms are reduced at creation).
+ * valHist has the capacity of errHist (maxIter); A_best, B_best, C_best,
+ * valHist, best_iter and stop_reason may be NULL.  device = -1 runs on the
+ * device set as tritd_als_masked_f64 does (the A rows of the best iterate are
+ * shard-local, B and C replicated; every shard takes the same decisions). */
+tritd_status tritd_als_holdout_f64(const double* X, const uint8_t* observed, const uint8_t* holdout,
+                                   int64_t n1, int64_t n2, int64_t n3, int32_t r,
+                                   const tritd_opts* opts, int32_t patience, const double* A0,
+                                   const double* B0, const double* C0, double* A, double* B,
+                                   double* C, double* errHist, int32_t* iters, double* A_best,
+                                   double* B_best, double* C_best, double* valHist,
+                                   int32_t* best_iter, int32_t* stop_reason, int32_t device);
 /* Steppable ALS session (bench, one process per GPU with comm; shard rows
  * [i0, i1) as for tritd_session_create; flags: TRITD_SESSION_D_ON_DEVICE).
  * quiet = 1 skips the every-5-iterations progress line (and its host
@@ -394,6 +430,31 @@ tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t de
  * entries of its shard (all of them without a mask).  Either may be NULL. */
 tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
                                          int64_t* observed_count);
+/* tritd_als_session_create_masked with a holdout mask (tritd_als_holdout_f64):
+ * holdout follows the conventions of observed (the mask byte of X(i0,0,0),
+ * fibres ldX BYTES apart, a device pointer exactly when
+ * TRITD_SESSION_D_ON_DEVICE is set); observed may be NULL (all true).  A run
+ * after a patience stop is a no-op, like one after a stop of :20.
+ * tritd_als_session_set_ncvx on such a session is TRITD_ERR_UNSUPPORTED. */
+tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t device,
+                                              const double* X, const uint8_t* observed,
+                                              const uint8_t* holdout, int64_t ldX, int64_t n1,
+                                              int64_t n2, int64_t n3, int64_t i0, int64_t i1,
+                                              int32_t r, const tritd_opts* opts, int32_t patience,
+                                              const double* A0, const double* B0, const double* C0,
+                                              tritd_comm* comm, uint32_t flags, int32_t quiet);
+/* The held-out entries (H & Omega) of the session's shard and
+ * ||H .* Omega .* X|| over all shards.  Either may be NULL. */
+tritd_status tritd_als_session_holdout_info(tritd_als_session* s, int64_t* count, double* norm);
+/* valHist (as many entries as errHist has; capacity maxIter), best_iter
+ * (0 before the first iteration) and stop_reason.  Any may be NULL.
+ * Synchronises. */
+tritd_status tritd_als_session_get_val(tritd_als_session* s, double* valHist, int32_t* best_iter,
+                                       int32_t* stop_reason);
+/* The factors iteration best_iter started with, shaped like those of
+ * tritd_als_session_get (A: the shard's rows).  Any may be NULL.  Synchronises.
+ * These three are TRITD_ERR_STATE on a session without a holdout. */
+tritd_status tritd_als_session_get_best(tritd_als_session* s, double* A, double* B, double* C);
 /* Turn an ALS session, masked or not, into the nonconvex solver of
  * fast_robust_triple_tensor/test.m:1-73 (the positional parameters of :1): the
  * outlier chain :36-48 fused into the fit, ridge 1e-12 + reweighted shrink on A

@@ -24,10 +24,13 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
                        int64_t n3, int64_t i0, int64_t i1, int r, int maxIter, double tol,
                        const double* A0, const double* B0, const double* C0, tritd_comm* comm,
                        uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                       const uint8_t* observed)
-    : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm) {
+                       const uint8_t* observed, const uint8_t* holdout, int patience)
+    : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm),
+      patience_(patience) {
+    if (holdout && patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
     try {  // (a constructor that throws runs no destructor: an all-false mask is refused here)
-        init(X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, flags, shared_stream, defer_norm, observed);
+        init(X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, flags, shared_stream, defer_norm, observed,
+             holdout);
     } catch (...) {
         release();
         throw;
@@ -37,7 +40,7 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
 void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
                       int64_t i1, int r, const double* A0, const double* B0, const double* C0,
                       uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                      const uint8_t* observed) {
+                      const uint8_t* observed, const uint8_t* holdout) {
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
     if (!rp_supported(g_.RP))
@@ -68,7 +71,7 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     }
     BtB_.alloc((size_t)g_.RP * g_.RP);
     CtC_.alloc((size_t)g_.RP * g_.RP);
-    red0_.alloc(2);
+    red0_.alloc(4);  // 2 per iteration; 4 at the creation of a holdout session
     red1_.alloc(red1_count());
     red2_.alloc(red2_count());
     fitpart_.alloc(2 * (size_t)als_fit_grid(g_));
@@ -79,6 +82,18 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
         TRITD_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), st_));
     TRITD_HIP(hipMalloc(&ctrl_, 4 * sizeof(int)));
     TRITD_HIP(hipMemsetAsync(ctrl_, 0, 4 * sizeof(int), st_));
+    if (holdout) {
+        holdout_ = true;
+        valHist_.alloc(errHist_.n);
+        hbest_.alloc(1);
+        Abest_.alloc(Ah_.n);
+        Bbest_.alloc(Bh_.n);
+        Cbest_.alloc(Ch_.n);
+        for (DBuf* b : {&valHist_, &hbest_})
+            TRITD_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), st_));
+        TRITD_HIP(hipMalloc(&hctrl_, 4 * sizeof(int)));
+        TRITD_HIP(hipMemsetAsync(hctrl_, 0, 4 * sizeof(int), st_));
+    }
 
     // X -> tile-major, and its TX copy for the mode-3 contraction (one-off)
     if (g_.n1l > 0) {
@@ -99,7 +114,8 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
         }
         // X <- Omega o X and the mask words (fill values, NaN included, never
         // enter: Xnorm below sees the zeroed X)
-        if (observed) pack_mask(observed, ldX, (flags & TRITD_SESSION_D_ON_DEVICE) != 0);
+        if (observed || holdout)
+            pack_mask(observed, ldX, (flags & TRITD_SESSION_D_ON_DEVICE) != 0, holdout);
     }
     // (a masked session's fit kernel writes the TX copy of the imputed
     // tensor in every iteration, before K2 reads it)
@@ -114,18 +130,38 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     TRITD_HIP(hipMemcpy(Bh_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
     TRITD_HIP(hipMemcpy(Ch_.p, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
     TRITD_HIP(hipMemcpy(ChT_.p, ChT.data(), ChT.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (holdout_) {  // best_iter = 0 until the first iteration: A0, B0, C0
+        TRITD_HIP(hipMemcpy(Abest_.p, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
+        TRITD_HIP(hipMemcpy(Bbest_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
+        TRITD_HIP(hipMemcpy(Cbest_.p, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
 
     // Xnorm = norm(X(:))  (:6)
     const int nb = sumsq_blocks(g_);
-    launch_sumsq_padded(g_, X_.p, sqpart_.p, nb, st_);
-    launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
-    if (masked_) {  // the observed count rides beside Xnorm^2 (summed over the shards)
+    if (holdout_) {
+        // X_ holds the held-out values: the same traversal with +0 in their
+        // place (bitwise the sum of the zeroed tensor), ||H o Omega o X||^2 beside it.
+        // red0 = {Xnorm^2, |Omega & ~H|, ||H o Omega o X||^2, |H & Omega|}
+        launch_sumsq_holdout(g_, X_.p, reinterpret_cast<const unsigned long long*>(M_.p), sqpart_.p,
+                             nb, st_);
+        launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
+        const double c[2] = {(double)obs_count_, (double)ho_count_};
+        TRITD_HIP(hipMemcpyAsync(red0_.p + 2, red0_.p + 1, sizeof(double), hipMemcpyDeviceToDevice,
+                                 st_));
+        TRITD_HIP(hipMemcpyAsync(red0_.p + 1, &c[0], sizeof(double), hipMemcpyHostToDevice, st_));
+        TRITD_HIP(hipMemcpyAsync(red0_.p + 3, &c[1], sizeof(double), hipMemcpyHostToDevice, st_));
+        TRITD_HIP(hipStreamSynchronize(st_));
+    } else {
+        launch_sumsq_padded(g_, X_.p, sqpart_.p, nb, st_);
+        launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
+    }
+    if (masked_ && !holdout_) {  // the observed count rides beside Xnorm^2 (summed over the shards)
         const double c = (double)obs_count_;
         TRITD_HIP(hipMemcpyAsync(red0_.p + 1, &c, sizeof(double), hipMemcpyHostToDevice, st_));
         TRITD_HIP(hipStreamSynchronize(st_));
     }
     if (!defer_norm) {
-        allreduce(red0_.p, 2);
+        allreduce(red0_.p, norm_count());
         set_norm_from_red0();
     }
     // Grams of the initial B, C (replicated)
@@ -141,6 +177,8 @@ void AlsSession::release() {
     ev_.clear();
     if (ctrl_) hip_quiet(hipFree(ctrl_));
     ctrl_ = nullptr;
+    if (hctrl_) hip_quiet(hipFree(hctrl_));
+    hctrl_ = nullptr;
     if (own_stream_ && st_) hip_quiet(hipStreamDestroy(st_));
     st_ = nullptr;
 }
@@ -148,41 +186,61 @@ void AlsSession::release() {
 AlsSession::~AlsSession() { release(); }
 
 void AlsSession::set_norm_from_red0() {
-    double ss[2];
-    TRITD_HIP(hipMemcpyAsync(ss, red0_.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+    double ss[4] = {0.0, 0.0, 0.0, 0.0};
+    TRITD_HIP(hipMemcpyAsync(ss, red0_.p, norm_count() * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     Xnorm_ = std::sqrt(ss[0]);
-    if (masked_ && ss[1] == 0.0)
-        throw Error(TRITD_ERR_ARG, "observed has no true entry: nothing to fit");
+    if ((masked_ || holdout_) && ss[1] == 0.0)
+        throw Error(TRITD_ERR_ARG, holdout_ ? "no observed entry is left to fit beside the holdout"
+                                            : "observed has no true entry: nothing to fit");
+    if (holdout_) {
+        Hnorm_ = std::sqrt(ss[2]);
+        if (ss[3] == 0.0) throw Error(TRITD_ERR_ARG, "holdout has no observed entry: nothing to score");
+        if (ss[2] == 0.0) throw Error(TRITD_ERR_ARG, "the held-out entries of X are all zero");
+    }
 }
 
 // observed -> M_ (and X zeroed where unobserved), as Session::pack_mask.  A
 // host mask is staged as a contiguous n1l x n2 x n3 byte array first.
-void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device) {
+// holdout (or null): a second byte mask of the same layout; the words are then
+// those of launch_mask_pack_holdout and X keeps its held-out values.
+void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
+                           const uint8_t* holdout) {
     masked_ = true;
-    M_.alloc_bytes((size_t)(g_.Ntm / 256) * MK_WORDS * sizeof(unsigned long long));
-    DBuf cnt, stage;
-    cnt.alloc(1);
-    TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
+    M_.alloc_bytes((size_t)(g_.Ntm / 256) * (holdout ? MK_WORDS_HO : MK_WORDS) *
+                   sizeof(unsigned long long));
+    DBuf cnt, stage, stageh;
+    cnt.alloc(2);
+    TRITD_HIP(hipMemsetAsync(cnt.p, 0, 2 * sizeof(double), st_));
     const uint8_t* src = observed;
+    const uint8_t* srch = holdout;
     int64_t ld = ldX;
     if (!on_device) {
         const size_t rows = (size_t)(g_.n2 * g_.n3);
-        stage.alloc_bytes((size_t)g_.n1l * rows);
-        if (ldX == g_.n1l)
-            TRITD_HIP(hipMemcpyAsync(stage.p, observed, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
-        else
-            TRITD_HIP(hipMemcpy2DAsync(stage.p, (size_t)g_.n1l, observed, (size_t)ldX, (size_t)g_.n1l,
-                                       rows, hipMemcpyHostToDevice, st_));
-        src = reinterpret_cast<const uint8_t*>(stage.p);
+        auto to_device = [&](DBuf& b, const uint8_t* m) {
+            b.alloc_bytes((size_t)g_.n1l * rows);
+            if (ldX == g_.n1l)
+                TRITD_HIP(hipMemcpyAsync(b.p, m, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
+            else
+                TRITD_HIP(hipMemcpy2DAsync(b.p, (size_t)g_.n1l, m, (size_t)ldX, (size_t)g_.n1l, rows,
+                                           hipMemcpyHostToDevice, st_));
+            return reinterpret_cast<const uint8_t*>(b.p);
+        };
+        if (observed) src = to_device(stage, observed);
+        if (holdout) srch = to_device(stageh, holdout);
         ld = g_.n1l;
     }
-    launch_mask_pack(g_, src, ld, reinterpret_cast<unsigned long long*>(M_.p), X_.p,
-                     reinterpret_cast<unsigned long long*>(cnt.p), st_);
-    unsigned long long c = 0;
-    TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
+    if (holdout)
+        launch_mask_pack_holdout(g_, src, srch, ld, reinterpret_cast<unsigned long long*>(M_.p),
+                                 X_.p, reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    else
+        launch_mask_pack(g_, src, ld, reinterpret_cast<unsigned long long*>(M_.p), X_.p,
+                         reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    unsigned long long c[2] = {0, 0};
+    TRITD_HIP(hipMemcpyAsync(c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
-    obs_count_ = (int64_t)c;
+    obs_count_ = (int64_t)c[0];
+    ho_count_ = (int64_t)c[1];
 }
 
 void AlsSession::allreduce(double* buf, int64_t count) {
@@ -198,6 +256,8 @@ int AlsSession::next_iter() {
 void AlsSession::enable_ncvx(const NcvxParams& p) {
     if (k_enq_ > 0 || ncvx_)
         throw Error(TRITD_ERR_STATE, "the nonconvex solver is chosen once, before the first run");
+    if (holdout_)
+        throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not supported by the nonconvex solver");
     if (!(p.rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
     // (a masked session: the fit kernel runs the outlier chain on
     // X~ = where(Omega, X, T) and writes XT_ every iteration, as the masked ALS)
@@ -221,6 +281,7 @@ void AlsSession::phaseFit(int k) {
     if (masked_) {  // X~ = where(Omega, X, Xhat) into XT_ for this iteration's K2
         a.M = reinterpret_cast<const unsigned long long*>(M_.p);
         a.XT = XT_.p;
+        a.holdout = holdout_ ? 1 : 0;
     }
     if (ncvx_) {  // test.m:35-48; O of iteration k-1 in buffer (k-1)&1, O of k into k&1
         a.ncvx = 1;
@@ -240,6 +301,15 @@ void AlsSession::phaseFit(int k) {
 
 void AlsSession::phaseErr(int k) {
     if (ncvx_) return;  // test.m takes errHist after the updates: phaseEnd
+    if (holdout_) {
+        // valHist(k), the running best and both stop tests; then the factors
+        // iteration k started with are kept if k is the best so far
+        launch_als_finish_holdout(red0_.p, Xnorm_, Hnorm_, k, tol_, patience_, errHist_.p,
+                                  valHist_.p, ctrl_, hctrl_, hbest_.p, st_);
+        launch_als_snapshot(Ah_.p, Bh_.p, Ch_.p, Abest_.p, Bbest_.p, Cbest_.p, (int64_t)Ah_.n,
+                            (int64_t)Bh_.n, (int64_t)Ch_.n, hctrl_, st_);
+        return;
+    }
     launch_als_finish(red0_.p, Xnorm_, k, tol_, errHist_.p, ctrl_, st_);
 }
 
@@ -392,6 +462,40 @@ void AlsSession::get(double* A, double* B, double* C, double* errHist, int* iter
         TRITD_HIP(hipMemcpy(errHist, errHist_.p, (size_t)done * sizeof(double),
                             hipMemcpyDeviceToHost));
     if (iters) *iters = done;
+}
+
+void AlsSession::get_val(double* valHist, int* best_iter, int* stop_reason) {
+    int done = 0, stopped = 0;
+    sync(&done, &stopped);
+    if (!holdout_) throw Error(TRITD_ERR_STATE, "get_val: not a holdout session");
+    int h[3];
+    TRITD_HIP(hipMemcpy(h, hctrl_, sizeof h, hipMemcpyDeviceToHost));
+    if (valHist && done > 0)
+        TRITD_HIP(hipMemcpy(valHist, valHist_.p, (size_t)done * sizeof(double),
+                            hipMemcpyDeviceToHost));
+    if (best_iter) *best_iter = h[0];
+    if (stop_reason) *stop_reason = h[2];
+}
+
+void AlsSession::get_best(double* A, double* B, double* C) {
+    int done = 0, stopped = 0;
+    sync(&done, &stopped);
+    if (!holdout_) throw Error(TRITD_ERR_STATE, "get_best: not a holdout session");
+    if (A) {
+        std::vector<double> h(Abest_.n);
+        TRITD_HIP(hipMemcpy(h.data(), Abest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unpack_A(g_, h, A);
+    }
+    if (B) {
+        std::vector<double> h(Bbest_.n);
+        TRITD_HIP(hipMemcpy(h.data(), Bbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unpack_B(g_, h, B);
+    }
+    if (C) {
+        std::vector<double> h(Cbest_.n);
+        TRITD_HIP(hipMemcpy(h.data(), Cbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unpack_C(g_, h, C);
+    }
 }
 
 void AlsSession::get_O(double* O, int64_t ldO) {

@@ -25,7 +25,8 @@ class AlsSession {
                int64_t i0, int64_t i1, int r, int maxIter, double tol, const double* A0,
                const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
                hipStream_t shared_stream = nullptr, bool defer_norm = false,
-               const uint8_t* observed = nullptr);
+               const uint8_t* observed = nullptr, const uint8_t* holdout = nullptr,
+               int patience = 0);
     ~AlsSession();
     AlsSession(const AlsSession&) = delete;
     AlsSession& operator=(const AlsSession&) = delete;
@@ -56,6 +57,25 @@ class AlsSession {
         if (masked) *masked = masked_ ? 1 : 0;
         if (observed_count) *observed_count = masked_ ? obs_count_ : g_.n1l * g_.n2 * g_.n3;
     }
+    // holdout (or null; a byte mask like observed): the entries of H & Omega are
+    // withheld from the fit, which is the masked ALS with observed = Omega & ~H,
+    // and scored every iteration in the fit kernel's own pass:
+    // valHist(k) = ||H o Omega o (X - Xhat)|| / ||H o Omega o X|| (tritd.h,
+    // tritd_als_holdout_f64).  patience > 0 stops the loop at k when
+    // k - best_iter >= patience.
+    bool holdout() const { return holdout_; }
+    // held-out entries of the shard, ||H o Omega o X|| over all shards
+    void holdout_info(int64_t* count, double* norm) const {
+        if (count) *count = ho_count_;
+        if (norm) *norm = Hnorm_;
+    }
+    // valHist(1:k), best_iter, stop_reason (0 none, 1 the test of :20, 2 patience)
+    void get_val(double* valHist, int* best_iter, int* stop_reason);
+    // the factors iteration best_iter started with (A0, B0, C0 before any run)
+    void get_best(double* A, double* B, double* C);
+    // doubles of the creation-time reduction: Xnorm^2, observed count
+    // (holdout: + ||H o Omega o X||^2, held-out count)
+    int norm_count() const { return holdout_ ? 4 : 2; }
     // O returned by test.m: that of iteration k-1 when the stop test broke
     // the loop at k (:67 before :71), else the last one; column-major shard
     void get_O(double* O, int64_t ldO);
@@ -110,10 +130,21 @@ class AlsSession {
     DBuf M_;
     bool masked_ = false;
     int64_t obs_count_ = 0;
-    void pack_mask(const uint8_t* observed, int64_t ldX, bool on_device);
+    void pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
+                   const uint8_t* holdout = nullptr);
+    // holdout=: M_ holds eight words per tile, X_ keeps the held-out values.
+    // Control words of their own: hctrl_[0] best_iter, [1] snapshot request,
+    // [2] stop_reason; hbest_[0] = valHist(best_iter).
+    bool holdout_ = false;
+    int patience_ = 0;
+    int64_t ho_count_ = 0;
+    double Hnorm_ = 0.0;
+    int* hctrl_ = nullptr;
+    DBuf valHist_, hbest_, Abest_, Bbest_, Cbest_;
     void init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
               int64_t i1, int r, const double* A0, const double* B0, const double* C0,
-              uint32_t flags, hipStream_t shared_stream, bool defer_norm, const uint8_t* observed);
+              uint32_t flags, hipStream_t shared_stream, bool defer_norm, const uint8_t* observed,
+              const uint8_t* holdout);
     void release();  // what the destructor frees beyond the members' own
 };
 

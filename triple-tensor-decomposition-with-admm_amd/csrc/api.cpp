@@ -595,13 +595,31 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
     if (iters) *iters = k;
 }
 
+// The holdout arguments of tritd_als_holdout_f64 (every output may be null).
+struct HoldoutArgs {
+    const uint8_t* holdout;
+    int patience;
+    double *A_best, *B_best, *C_best, *valHist;
+    int32_t *best_iter, *stop_reason;
+};
+
+// A rows of the best iterate are shard-local, B and C replicated; every
+// shard holds the same valHist and decisions (the sums are all-reduced).
+void get_holdout(AlsSession& s, int p, const HoldoutArgs& h) {
+    int bi = 0, sr = 0;
+    s.get_val(p == 0 ? h.valHist : nullptr, &bi, &sr);
+    s.get_best(h.A_best, p == 0 ? h.B_best : nullptr, p == 0 ? h.C_best : nullptr);
+    if (p == 0 && h.best_iter) *h.best_iter = bi;
+    if (p == 0 && h.stop_reason) *h.stop_reason = sr;
+}
+
 // triple_decomp_ALS over a device set: the ALS phases (als.cpp) with the
 // fit sum, [M2 | A^TA] and M3 reduced between them.
 void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
                           int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
                           const double* B0, const double* C0, double* A, double* B, double* C,
                           double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O,
-                          const uint8_t* observed);
+                          const uint8_t* observed, const HoldoutArgs* ho);
 
 // triple_decomp_ALS / the test.m solver over a device set: one AlsSession
 // per shard with a communicator (its run() carries the fit-sum, [M2 | A^TA]
@@ -612,12 +630,13 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
                    int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
                    const double* B0, const double* C0, double* A, double* B, double* C,
                    double* errHist, int32_t* iters, const NcvxParams* ncvx = nullptr,
-                   double* O = nullptr, const uint8_t* observed = nullptr) {
+                   double* O = nullptr, const uint8_t* observed = nullptr,
+                   const HoldoutArgs* ho = nullptr) {
     {
         const char* sh = std::getenv("TRITD_SHOV");
         if (sh && std::atoi(sh) == 0) {
             run_als_group_serial(devs, X, n1, n2, n3, r, maxIter, tol, A0, B0, C0, A, B, C, errHist,
-                                 iters, ncvx, O, observed);
+                                 iters, ncvx, O, observed, ho);
             return;
         }
     }
@@ -626,11 +645,13 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
         const auto [i0, i1] = grp.rows(p, n1);
         AlsSession s(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0, B0, C0,
                      grp.size() > 1 ? comm : nullptr, 0, nullptr, false,
-                     observed ? observed + i0 : nullptr);
+                     observed ? observed + i0 : nullptr, ho ? ho->holdout + i0 : nullptr,
+                     ho ? ho->patience : 0);
         if (ncvx) s.enable_ncvx(*ncvx);
         s.run(maxIter);
         int k = 0;
         s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr, p == 0 ? errHist : nullptr, &k);
+        if (ho) get_holdout(s, p, *ho);
         if (ncvx && O) s.get_O(O + s.geom().i0, n1);
         if (p == 0 && iters) *iters = k;
         return s.flags();
@@ -641,7 +662,7 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
                           int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
                           const double* B0, const double* C0, double* A, double* B, double* C,
                           double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O,
-                          const uint8_t* observed) {
+                          const uint8_t* observed, const HoldoutArgs* ho) {
     DeviceGroup grp(devs, n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<AlsSession>> ss;
@@ -650,11 +671,12 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new AlsSession(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0,
                                        B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true,
-                                       observed ? observed + i0 : nullptr));
+                                       observed ? observed + i0 : nullptr,
+                                       ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0));
         if (ncvx) ss.back()->enable_ncvx(*ncvx);
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
-    grp.reduce(ss, &AlsSession::red0, 2);
+    grp.reduce(ss, &AlsSession::red0, ss[0]->norm_count());
     each([](AlsSession& s) { s.set_norm_from_red0(); });
     for (int it = 0; it < maxIter; ++it) {
         int k = 0;
@@ -681,6 +703,7 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         TRITD_HIP(hipSetDevice(devs[p]));
         ss[p]->get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr, p == 0 ? errHist : nullptr, &k);
         if (ncvx && O) ss[p]->get_O(O + ss[p]->geom().i0, n1);
+        if (ho) get_holdout(*ss[p], p, *ho);
         g_last_flags |= ss[p]->flags();
     }
     if (iters) *iters = k;
@@ -1146,6 +1169,40 @@ tritd_status tritd_als_masked_f64(const double* X, const uint8_t* observed, int6
     });
 }
 
+tritd_status tritd_als_holdout_f64(const double* X, const uint8_t* observed, const uint8_t* holdout,
+                                   int64_t n1, int64_t n2, int64_t n3, int32_t r,
+                                   const tritd_opts* opts, int32_t patience, const double* A0,
+                                   const double* B0, const double* C0, double* A, double* B,
+                                   double* C, double* errHist, int32_t* iters, double* A_best,
+                                   double* B_best, double* C_best, double* valHist,
+                                   int32_t* best_iter, int32_t* stop_reason, int32_t device) {
+    std::lock_guard<std::mutex> lk(g_mutex);
+    g_last_flags = 0;
+    return guarded([&] {
+        check_als_opts(opts);
+        check_dims(n1, n2, n3, r);
+        need(X, "X"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
+        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+        const int maxIter = opts->maxIter < 0 ? 0 : opts->maxIter;
+        const HoldoutArgs ho{holdout, patience, A_best, B_best, C_best, valHist, best_iter,
+                             stop_reason};
+        if (device < 0 && g_devices.size() > 1) {
+            run_als_group(g_devices, X, n1, n2, n3, r, maxIter, opts->tol, A0, B0, C0, A, B, C,
+                          errHist, iters, nullptr, nullptr, observed, &ho);
+            return;
+        }
+        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
+        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, maxIter, opts->tol, A0, B0, C0, nullptr, 0,
+                     nullptr, false, observed, holdout, patience);
+        s.run(maxIter);
+        int k = 0;
+        s.get(A, B, C, errHist, &k);
+        get_holdout(s, 0, ho);
+        g_last_flags |= s.flags();
+        if (iters) *iters = k;
+    });
+}
+
 tritd_status tritd_als_sharded_virtual_f64(const double* X, int64_t n1, int64_t n2, int64_t n3,
                                            int32_t r, const tritd_opts* opts, const double* A0,
                                            const double* B0, const double* C0, int32_t nshards,
@@ -1217,6 +1274,29 @@ tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, c
                                            A0, B0, C0, comm, flags, quiet);
 }
 
+// the checks and the construction shared by the three session creators
+static void als_session_create(tritd_als_session** out, int32_t device, const double* X,
+                        const uint8_t* observed, const uint8_t* holdout, int32_t patience,
+                        int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0, int64_t i1,
+                        int32_t r, const tritd_opts* opts, const double* A0, const double* B0,
+                        const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet) {
+    need(out, "out");
+    *out = nullptr;
+    check_als_opts(opts);
+    check_dims(n1, n2, n3, r);
+    need(X, "X"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
+    if (flags & ~(uint32_t)TRITD_SESSION_D_ON_DEVICE)
+        throw Error(TRITD_ERR_UNSUPPORTED, "ALS sessions are fp64 (flags: D_ON_DEVICE only)");
+    if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
+    if (ldX < i1 - i0) throw Error(TRITD_ERR_ARG, "ldX smaller than the shard");
+    const int dev = pick_device(device);
+    auto* s = new AlsSession(dev, X, ldX, n1, n2, n3, i0, i1, r,
+                             opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0, comm,
+                             flags, nullptr, false, observed, holdout, patience);
+    s->set_quiet(quiet != 0);
+    *out = reinterpret_cast<tritd_als_session*>(s);
+}
+
 tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t device,
                                              const double* X, const uint8_t* observed, int64_t ldX,
                                              int64_t n1, int64_t n2, int64_t n3, int64_t i0,
@@ -1224,21 +1304,52 @@ tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t de
                                              const double* A0, const double* B0, const double* C0,
                                              tritd_comm* comm, uint32_t flags, int32_t quiet) {
     return guarded([&] {
+        als_session_create(out, device, X, observed, nullptr, 0, ldX, n1, n2, n3, i0, i1, r, opts, A0,
+                           B0, C0, comm, flags, quiet);
+    });
+}
+
+tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t device,
+                                              const double* X, const uint8_t* observed,
+                                              const uint8_t* holdout, int64_t ldX, int64_t n1,
+                                              int64_t n2, int64_t n3, int64_t i0, int64_t i1,
+                                              int32_t r, const tritd_opts* opts, int32_t patience,
+                                              const double* A0, const double* B0, const double* C0,
+                                              tritd_comm* comm, uint32_t flags, int32_t quiet) {
+    return guarded([&] {
         need(out, "out");
         *out = nullptr;
-        check_als_opts(opts);
-        check_dims(n1, n2, n3, r);
-        need(X, "X"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (flags & ~(uint32_t)TRITD_SESSION_D_ON_DEVICE)
-            throw Error(TRITD_ERR_UNSUPPORTED, "ALS sessions are fp64 (flags: D_ON_DEVICE only)");
-        if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
-        if (ldX < i1 - i0) throw Error(TRITD_ERR_ARG, "ldX smaller than the shard");
-        const int dev = pick_device(device);
-        auto* s = new AlsSession(dev, X, ldX, n1, n2, n3, i0, i1, r,
-                                 opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0,
-                                 comm, flags, nullptr, false, observed);
-        s->set_quiet(quiet != 0);
-        *out = reinterpret_cast<tritd_als_session*>(s);
+        need(holdout, "holdout");
+        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+        als_session_create(out, device, X, observed, holdout, patience, ldX, n1, n2, n3, i0, i1, r,
+                           opts, A0, B0, C0, comm, flags, quiet);
+    });
+}
+
+tritd_status tritd_als_session_holdout_info(tritd_als_session* s, int64_t* count, double* norm) {
+    return guarded([&] {
+        need(s, "session");
+        auto* as = reinterpret_cast<AlsSession*>(s);
+        if (!as->holdout()) throw Error(TRITD_ERR_STATE, "holdout_info: not a holdout session");
+        as->holdout_info(count, norm);
+    });
+}
+
+tritd_status tritd_als_session_get_val(tritd_als_session* s, double* valHist, int32_t* best_iter,
+                                       int32_t* stop_reason) {
+    return guarded([&] {
+        need(s, "session");
+        int bi = 0, sr = 0;
+        reinterpret_cast<AlsSession*>(s)->get_val(valHist, &bi, &sr);
+        if (best_iter) *best_iter = bi;
+        if (stop_reason) *stop_reason = sr;
+    });
+}
+
+tritd_status tritd_als_session_get_best(tritd_als_session* s, double* A, double* B, double* C) {
+    return guarded([&] {
+        need(s, "session");
+        reinterpret_cast<AlsSession*>(s)->get_best(A, B, C);
     });
 }
 

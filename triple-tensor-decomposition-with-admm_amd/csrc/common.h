@@ -154,6 +154,9 @@ constexpr int CE_IMG = 256 + 64;
 // position 64 w + l of the compact-E bytes above) is observed.  Padding rows
 // and padded t are marked observed: they behave as without a mask.
 constexpr int MK_WORDS = 4;
+// A holdout session (ALS, holdout=) packs eight words per tile, at M + 8 b:
+// words 0-3 as above for the fit mask Omega & ~H, words 4-7 for H & Omega.
+constexpr int MK_WORDS_HO = 8;
 
 __host__ __device__ inline int64_t tm_tile_base(int64_t g, int64_t tt, int64_t ntt) {
     return ((((g >> 2) * ntt + tt) << 2) + (g & 3)) << 8;

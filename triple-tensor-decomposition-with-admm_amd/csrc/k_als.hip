@@ -30,6 +30,12 @@
 // values of the chain for x = L, O = Lambda = Gamma = 0 are imposed per element
 // (O_new = 0, an increment of exactly 0 to Lambda and Gamma, a residual of
 // exactly 0) instead of being left to the rounding of (L + rho L)/(1 + rho).
+//
+// HO (held-out validation, holdout=; with MK, without NCV): the
+// tile has eight mask words, 0-3 the fit mask Omega & ~H and 4-7 H & Omega.
+// The fit path is the MK one on words 0-3; a second accumulator sums
+// (X - Xhat)^2 over the held-out elements (X keeps its value there) into
+// partial[2b + 1], so valHist comes out of the pass that computes errHist.
 #include "kernels.h"
 
 namespace tritd {
@@ -48,7 +54,7 @@ __device__ __forceinline__ d4 als_mfma4(double a, double b, d4 c) {
 __device__ __forceinline__ double nc_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : x); }
 
 // One tile's registers: x = X; NCV: e = O, Lam, Gam of the same tile; MK: lane
-// l holds mask word l & 3 of the tile.  (The unmasked forms have no mask
+// l holds mask word l & 3 of the tile (HO: l & 7 of eight).  (The unmasked forms have no mask
 // member, so they compile as before the mask existed.)
 template <bool NCV, bool MK>
 struct FitRegs {
@@ -62,9 +68,10 @@ struct FitRegs<NCV, true> {
     u2v mk;
 };
 
-template <int RP, bool NCV, bool MK = false>
+template <int RP, bool NCV, bool MK = false, bool HO = false>
 __global__ __launch_bounds__(64 * FIT_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_als_fit(AlsFitArgs a) {
+    static_assert(!HO || (MK && !NCV), "the held-out form is a masked ALS fit");
     if (*a.stop) return;
     constexpr int KS = RP / 4;    // K-steps of the L MFMA
     constexpr int MT = RP / 16;   // k-tiles of W
@@ -128,6 +135,7 @@ void k_als_fit(AlsFitArgs a) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) wacc[m] = d4{0.0, 0.0, 0.0, 0.0};
     double ss = 0.0;
+    double sh = 0.0;  // HO: sum (X - Xhat)^2 over the held-out elements
     const d2v* X2 = reinterpret_cast<const d2v*>(a.X);
 
     // Two named register sets, the t-walk unrolled by two (a copy cur = next
@@ -146,8 +154,9 @@ void k_als_fit(AlsFitArgs a) {
             // one 32 B piece per wave, typed as a global load (a flat load's
             // completion cannot be counted: every vmcnt wait of the walk
             // would become vmcnt(0), k_admm.hip)
+            // (HO: one 64 B piece, words 0-3 the fit mask, 4-7 the held-out set)
             nx.mk = *(const __attribute__((address_space(1))) u2v*)(
-                a.M + ((tm_tile_base(tile, tt, ntt) >> 8) << 2) + (lane & 3));
+                a.M + ((tm_tile_base(tile, tt, ntt) >> 8) << (HO ? 3 : 2)) + (lane & (HO ? 7 : 3)));
         if constexpr (NCV) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -184,6 +193,16 @@ void k_als_fit(AlsFitArgs a) {
                     ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cx.mk[1], r) << 32) |
                     (uint32_t)__builtin_amdgcn_readlane((int)cx.mk[0], r);
                 ob[r] = __builtin_amdgcn_inverse_ballot_w64(ow);
+                if constexpr (HO) {
+                    // valHist: a select, not a product (X is 0, not NaN, where
+                    // unobserved; a held-out X may be anything finite)
+                    const uint64_t hw =
+                        ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)cx.mk[1], 4 + r) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane((int)cx.mk[0], 4 + r);
+                    const double dh =
+                        __builtin_amdgcn_inverse_ballot_w64(hw) ? xr[r] - lacc[r] : 0.0;
+                    sh += dh * dh;
+                }
                 xr[r] = ob[r] ? xr[r] : lacc[r];  // X~ = where(Omega, X, Xhat)
             }
             // X~ -> "TX" order (common.h): lane l, slot s holds X~(ij = 4s+(l>>4), t = l&15)
@@ -281,17 +300,32 @@ void k_als_fit(AlsFitArgs a) {
             for (int rr = 0; rr < 4; ++rr)
                 a.Wk[(int64_t)(16 * m + tg + 4 * rr) * a.plane + wbase] = wacc[m][rr];
     }
-    // fixed-order block reduction (pairs: the second is 0, k_reduce_pairs)
+    // fixed-order block reduction (pairs: the second is 0, k_reduce_pairs;
+    // HO: the held-out sum)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    if constexpr (HO) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sh += __shfl_xor(sh, off);
+    }
     __shared__ double red[FIT_WAVES];
+    __shared__ double redh[HO ? FIT_WAVES : 1];
     if (lane == 0) red[wid] = ss;
+    if constexpr (HO) {
+        if (lane == 0) redh[wid] = sh;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         double x = 0.0;
         for (int w = 0; w < FIT_WAVES; ++w) x += red[w];
         a.partial[2 * blockIdx.x] = x;
-        a.partial[2 * blockIdx.x + 1] = 0.0;
+        if constexpr (HO) {
+            double y = 0.0;
+            for (int w = 0; w < FIT_WAVES; ++w) y += redh[w];
+            a.partial[2 * blockIdx.x + 1] = y;
+        } else {
+            a.partial[2 * blockIdx.x + 1] = 0.0;
+        }
     }
 }
 
@@ -300,9 +334,13 @@ int als_fit_grid(const Geom& g) { return (int)cdiv(g.tiles, FIT_WAVES); }
 void launch_als_fit(const Geom& g, const AlsFitArgs& a, hipStream_t st) {
     const dim3 grid(als_fit_grid(g)), block(64 * FIT_WAVES);
     if (a.M && !a.XT) throw Error(TRITD_ERR_UNSUPPORTED, "the masked ALS fit needs XT");
+    if (a.holdout && (!a.M || a.ncvx))
+        throw Error(TRITD_ERR_UNSUPPORTED, "the held-out fit is a masked ALS fit");
 #define FIT_CASE(RPV)                                                                  \
     case RPV:                                                                          \
-        if (a.ncvx && a.M)                                                             \
+        if (a.holdout)                                                                 \
+            hipLaunchKernelGGL((k_als_fit<RPV, false, true, true>), grid, block, 0, st, a); \
+        else if (a.ncvx && a.M)                                                        \
             hipLaunchKernelGGL((k_als_fit<RPV, true, true>), grid, block, 0, st, a);   \
         else if (a.ncvx)                                                               \
             hipLaunchKernelGGL((k_als_fit<RPV, true>), grid, block, 0, st, a);         \
@@ -338,6 +376,77 @@ __global__ void k_als_finish(const double* ss, double Xnorm, int k, double tol, 
 void launch_als_finish(const double* ss, double Xnorm, int k, double tol, double* errHist,
                        int* ctrl, hipStream_t st) {
     hipLaunchKernelGGL(k_als_finish, dim3(1), dim3(1), 0, st, ss, Xnorm, k, tol, errHist, ctrl);
+    TRITD_CHECK_LAUNCH();
+}
+
+// The finish of a holdout session: errHist(k) as above and
+// valHist(k) = sqrt(ss[1]) / Hnorm, the running best (a strict < against it,
+// k = 1 always taken), then the stop test of :20, then the patience test
+// k - best_iter >= patience (patience > 0 only).  hctrl[0] = best_iter,
+// hctrl[1] = snapshot request of this iteration (k_als_snapshot),
+// hctrl[2] = stop_reason (0 none, 1 the test of :20, 2 patience); best[0] =
+// valHist(best_iter).  An iteration enqueued after a stop clears the request.
+__global__ void k_als_finish_ho(const double* ss, double Xnorm, double Hnorm, int k, double tol,
+                                int patience, double* errHist, double* valHist, int* ctrl,
+                                int* hctrl, double* best) {
+    if (ctrl[0]) {
+        hctrl[1] = 0;
+        return;
+    }
+    const double e = sqrt(ss[0]) / Xnorm;
+    const double v = sqrt(ss[1]) / Hnorm;
+    errHist[k - 1] = e;
+    valHist[k - 1] = v;
+    ctrl[1] = k;
+    int snap = 0;
+    if (k == 1 || v < best[0]) {
+        best[0] = v;
+        hctrl[0] = k;
+        snap = 1;
+    }
+    hctrl[1] = snap;
+    if (k > 1 && fabs(e - errHist[k - 2]) < tol * errHist[k - 2]) {
+        ctrl[0] = 1;
+        hctrl[2] = 1;
+    } else if (patience > 0 && k - hctrl[0] >= patience) {
+        ctrl[0] = 1;
+        hctrl[2] = 2;
+    }
+}
+
+void launch_als_finish_holdout(const double* ss, double Xnorm, double Hnorm, int k, double tol,
+                               int patience, double* errHist, double* valHist, int* ctrl,
+                               int* hctrl, double* best, hipStream_t st) {
+    hipLaunchKernelGGL(k_als_finish_ho, dim3(1), dim3(1), 0, st, ss, Xnorm, Hnorm, k, tol, patience,
+                       errHist, valHist, ctrl, hctrl, best);
+    TRITD_CHECK_LAUNCH();
+}
+
+// Ah, Bh, Ch -> the best-iterate copies when the finish asked for it (the
+// factors iteration best_iter started with: it runs before the A update).
+__global__ __launch_bounds__(256) void k_als_snapshot(const double* __restrict__ Ah,
+                                                      const double* __restrict__ Bh,
+                                                      const double* __restrict__ Ch, double* Ab,
+                                                      double* Bb, double* Cb, int64_t na, int64_t nb,
+                                                      int64_t nc, const int* hctrl) {
+    if (!hctrl[1]) return;
+    const int64_t n = na + nb + nc;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        if (e < na)
+            Ab[e] = Ah[e];
+        else if (e < na + nb)
+            Bb[e - na] = Bh[e - na];
+        else
+            Cb[e - na - nb] = Ch[e - na - nb];
+    }
+}
+
+void launch_als_snapshot(const double* Ah, const double* Bh, const double* Ch, double* Ab,
+                         double* Bb, double* Cb, int64_t na, int64_t nb, int64_t nc,
+                         const int* hctrl, hipStream_t st) {
+    const int64_t n = na + nb + nc;
+    hipLaunchKernelGGL(k_als_snapshot, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 1024)),
+                       dim3(256), 0, st, Ah, Bh, Ch, Ab, Bb, Cb, na, nb, nc, hctrl);
     TRITD_CHECK_LAUNCH();
 }
 

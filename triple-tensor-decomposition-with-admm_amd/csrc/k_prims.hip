@@ -32,6 +32,45 @@ __global__ __launch_bounds__(256) void k_sumsq(const double* __restrict__ X, int
     }
 }
 
+// k_sumsq over a holdout session's tensor: the same traversal and reduction,
+// a held-out element (bit l of word 4 + r of its tile, common.h) replaced by 0
+// in the first sum and taken alone in the second
+__global__ __launch_bounds__(256) void k_sumsq_holdout(const double* __restrict__ X,
+                                                       const unsigned long long* __restrict__ M,
+                                                       int64_t n, double* partial) {
+    double s = 0.0, h = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int w = (int)(e & 255);
+        const int r = ((w >> 7) << 1) | (w & 1), l = (w & 127) >> 1;
+        const bool ho = (M[(e >> 8) * MK_WORDS_HO + 4 + r] >> l) & 1ull;
+        const double x = X[e];
+        const double xf = ho ? 0.0 : x, xh = ho ? x : 0.0;
+        s = fma(xf, xf, s);
+        h = fma(xh, xh, h);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_xor(s, off);
+        h += __shfl_xor(h, off);
+    }
+    __shared__ double red[4], redh[4];
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = s;
+        redh[threadIdx.x >> 6] = h;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+        partial[2 * blockIdx.x + 1] = ((redh[0] + redh[1]) + redh[2]) + redh[3];
+    }
+}
+
+void launch_sumsq_holdout(const Geom& g, const double* X, const unsigned long long* M,
+                          double* partial, int nblocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_sumsq_holdout, dim3(nblocks), dim3(256), 0, st, X, M, g.Ntm, partial);
+    TRITD_CHECK_LAUNCH();
+}
+
 int sumsq_blocks(const Geom& g) {
     int64_t b = cdiv(g.Ntm, 256 * 8);
     return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
@@ -704,6 +743,51 @@ void launch_mask_pack(const Geom& g, const uint8_t* obs, int64_t ld, unsigned lo
     const int64_t ntiles = g.Ntm / 256;
     hipLaunchKernelGGL(k_mask_pack, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, st, obs, ld,
                        g.n1l, g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
+    TRITD_CHECK_LAUNCH();
+}
+
+// k_mask_pack for a holdout session: obs (null: all observed) and hold -> eight
+// words per tile, 0-3 the fit mask Omega & ~H, 4-7 H & Omega.  D is zeroed only
+// where unobserved (a held-out value stays for valHist); padding is
+// fit-observed and never held out; both sets are counted.
+__global__ __launch_bounds__(256) void k_mask_pack_holdout(
+    const uint8_t* __restrict__ obs, const uint8_t* __restrict__ hold, int64_t ld, int64_t n1l,
+    int64_t n2, int64_t n3, int64_t n1p, int64_t ntt, int64_t ntiles,
+    unsigned long long* __restrict__ M, double* __restrict__ D, unsigned long long* count) {
+    const int l = threadIdx.x & 63;
+    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // tile ordinal
+    if (blk >= ntiles) return;
+    const int64_t q4 = blk >> 2, grp = q4 / ntt, tt = q4 - grp * ntt;
+    const int64_t g = grp * 4 + (blk & 3);
+    const int64_t row = 16 * g + (l & 15);
+    const int64_t j = row / n1p, i = row - j * n1p;
+    int fitn = 0, hon = 0;
+#pragma unroll
+    for (int w = 0; w < MK_WORDS; ++w) {
+        const int64_t t = 16 * tt + (l >> 4) + 4 * w;
+        const bool real = i < n1l && j < n2 && t < n3;
+        const int64_t o = real ? (t * n2 + j) * ld + i : 0;
+        const bool on = !real || !obs || obs[o] != 0;
+        const bool ho = real && on && hold[o] != 0;
+        const unsigned long long fw = __ballot(on && !ho), hw = __ballot(ho);
+        fitn += __builtin_popcountll(__ballot(real && on && !ho));
+        hon += __builtin_popcountll(hw);
+        if (l == w) {
+            M[blk * MK_WORDS_HO + w] = fw;
+            M[blk * MK_WORDS_HO + 4 + w] = hw;
+        }
+        if (!on) D[(blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1)] = 0.0;
+    }
+    if (l == 0 && fitn) atomicAdd(count, (unsigned long long)fitn);
+    if (l == 0 && hon) atomicAdd(count + 1, (unsigned long long)hon);
+}
+
+void launch_mask_pack_holdout(const Geom& g, const uint8_t* obs, const uint8_t* hold, int64_t ld,
+                              unsigned long long* M, double* D, unsigned long long* count,
+                              hipStream_t st) {
+    const int64_t ntiles = g.Ntm / 256;
+    hipLaunchKernelGGL(k_mask_pack_holdout, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, st, obs,
+                       hold, ld, g.n1l, g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
     TRITD_CHECK_LAUNCH();
 }
 

@@ -208,6 +208,18 @@ void launch_from_tm(const Geom& g, const double* src, double* dst, int64_t ld, h
 // of the shard (pads excluded) added to *count
 void launch_mask_pack(const Geom& g, const uint8_t* obs, int64_t ld, unsigned long long* M,
                       double* D, unsigned long long* count, hipStream_t st);
+// holdout=: obs (or null: all observed) and hold are byte masks like obs above.
+// Eight words per tile (MK_WORDS_HO): 0-3 the fit mask Omega & ~H, 4-7 H & Omega.
+// D is zeroed where unobserved only (the held-out values stay); padding is
+// fit-observed and never held out; count[0] += |Omega & ~H|, count[1] += |H & Omega|
+void launch_mask_pack_holdout(const Geom& g, const uint8_t* obs, const uint8_t* hold, int64_t ld,
+                              unsigned long long* M, double* D, unsigned long long* count,
+                              hipStream_t st);
+// launch_sumsq_padded over a holdout session's D and mask words: partial[2b] is
+// that of the tensor with the held-out entries zeroed (bitwise: they add +0),
+// partial[2b + 1] the sum of squares of the held-out entries
+void launch_sumsq_holdout(const Geom& g, const double* X, const unsigned long long* M,
+                          double* partial, int nblocks, hipStream_t st);
 void launch_soft_threshold(const double* X, int64_t n, double lam, double* Y, hipStream_t st);
 void launch_design(char which, const double* P, const double* Q, int64_t nP, int64_t nQ, int r,
                    double* out, hipStream_t st);
@@ -235,11 +247,25 @@ struct AlsFitArgs {
     // Xhat) the kernel writes for this iteration's K2; X holds Omega o X
     const unsigned long long* M;
     double* XT;
+    // held-out form (holdout=; != 0 with M and without ncvx): M holds the
+    // eight words per tile of launch_mask_pack_holdout, X keeps its value at
+    // a held-out entry, and partial[2b + 1] = sum (X - Xhat)^2 over H & Omega
+    int holdout;
 };
 int als_fit_grid(const Geom& g);
 void launch_als_fit(const Geom& g, const AlsFitArgs& a, hipStream_t st);
 void launch_als_finish(const double* ss, double Xnorm, int k, double tol, double* errHist,
                        int* ctrl, hipStream_t st);
+// holdout sessions: errHist(k), valHist(k), the running best,
+// the stop test of :20, then the patience test; hctrl = {best_iter, snapshot
+// request, stop_reason}, best[0] = valHist(best_iter)
+void launch_als_finish_holdout(const double* ss, double Xnorm, double Hnorm, int k, double tol,
+                               int patience, double* errHist, double* valHist, int* ctrl,
+                               int* hctrl, double* best, hipStream_t st);
+// copies Ah, Bh, Ch (na, nb, nc doubles) when hctrl[1] is set
+void launch_als_snapshot(const double* Ah, const double* Bh, const double* Ch, double* Ab,
+                         double* Bb, double* Cb, int64_t na, int64_t nb, int64_t nc,
+                         const int* hctrl, hipStream_t st);
 void launch_tm_to_tx(const Geom& g, const double* src, double* dst, hipStream_t st);
 // test.m:82-92: A1 <- sign(A1).*max(|A1| - gamma*(1./((|A1|+eps).^expo)), 0), into Ah and AhT
 void launch_ncvx_shrink(const Geom& g, double* Ah, double* AhT, double gamma, double eps,

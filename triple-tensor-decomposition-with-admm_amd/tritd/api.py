@@ -92,13 +92,13 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
-def _observed_bytes(observed, shape, what="D"):
+def _observed_bytes(observed, shape, what="D", name="observed"):
     """opts.observed -> a column-major uint8 array of D's shape (nonzero =
     observed); a shape that differs from D's raises like a MATLAB logical
     index of the wrong size."""
     m = np.asarray(observed)
     if tuple(m.shape) != tuple(shape):
-        raise ValueError(f"observed must have the shape of {what} {tuple(shape)}, got {tuple(m.shape)}")
+        raise ValueError(f"{name} must have the shape of {what} {tuple(shape)}, got {tuple(m.shape)}")
     return np.asfortranarray(m != 0).view(np.uint8)
 
 
@@ -285,7 +285,7 @@ def make_als_opts(opts):
 
 
 def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, return_iters=False,
-                      virtual_shards=0, observed=None):
+                      virtual_shards=0, observed=None, holdout=None, patience=0):
     """[A,B,C,errHist] = triple_decomp_ALS(X, r, opts) on the GPU
     (fast_robust_triple_tensor/triple_decomp_ALS.m:1-40).
 
@@ -294,6 +294,17 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
     entries are never used (NaN allowed), the updates see the current model
     there, and errHist counts observed entries only.  For mode-1 shards set
     the device set (``set_devices``), not ``virtual_shards``.
+
+    ``holdout`` (a logical array of X's shape; tritd_als_holdout_f64) withholds
+    the entries of ``holdout & observed`` from the fit, which is exactly the
+    masked one with ``observed & ~holdout``, and scores them every iteration in
+    the fit kernel's own pass: ``valHist(k) = ||H o Omega o (X - Xhat)|| /
+    ||H o Omega o X||`` for the factors iteration k started with.  The returned
+    tuple then gains a trailing dict with ``valHist``, ``best_iter`` (the first
+    minimum of valHist), ``stop_reason`` (0 maxIter, 1 the test of :20,
+    2 patience), ``A_best, B_best, C_best`` (the factors iteration best_iter
+    started with) and ``holdout_count``.  ``patience = p > 0`` stops the loop
+    at k once ``k - best_iter >= p``.
 
     The initial factors are drawn here in the order of :8-10 unless given
     (MATLAB's randn is not reproducible outside MATLAB).  The progress line of
@@ -309,6 +320,11 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
         obs = _observed_bytes(observed, X.shape, "X")
         if virtual_shards and virtual_shards > 1:
             raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
+    hold = None
+    if holdout is not None:
+        hold = _observed_bytes(holdout, X.shape, "X", "holdout")
+        if virtual_shards and virtual_shards > 1:
+            raise ValueError("holdout with virtual_shards: use set_devices([d] * P) and device=-1")
     if A0 is None or B0 is None or C0 is None:
         A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
     else:
@@ -318,6 +334,24 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
     Cf = np.zeros((r, r, n3), order="F")
     errHist = np.zeros(max(o.maxIter, 1))
     k = _lib.i32(0)
+    if hold is not None:
+        Ab, Bb, Cb = np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cf)
+        valHist = np.zeros(max(o.maxIter, 1))
+        best, why = _lib.i32(0), _lib.i32(0)
+        check_flags(lib.tritd_als_holdout_f64(_ptr(X), _ptr(obs), _ptr(hold), n1, n2, n3, r,
+                                              C.byref(o), int(patience), _ptr(A0), _ptr(B0),
+                                              _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(errHist),
+                                              C.byref(k), _ptr(Ab), _ptr(Bb), _ptr(Cb),
+                                              _ptr(valHist), C.byref(best), C.byref(why),
+                                              int(device)), "triple_decomp_ALS")
+        count = int(np.count_nonzero(hold if obs is None else hold & obs))
+        out = [A, B, Cf, errHist[: k.value].copy()]
+        if return_iters:
+            out.append(k.value)
+        out.append(dict(valHist=valHist[: k.value].copy(), best_iter=best.value,
+                        stop_reason=why.value, A_best=Ab, B_best=Bb, C_best=Cb,
+                        holdout_count=count))
+        return tuple(out)
     if virtual_shards and virtual_shards > 1:
         check_flags(lib.tritd_als_sharded_virtual_f64(_ptr(X), n1, n2, n3, r, C.byref(o), _ptr(A0),
                                                 _ptr(B0), _ptr(C0), int(virtual_shards), _ptr(A),
@@ -603,12 +637,20 @@ class AlsSession:
     masked or not, into the nonconvex solver of test.m:1-73
     (tritd_als_session_set_ncvx; ``triple_decomp_ncvx`` stepped): ``get_O``
     then returns the shard's O, and with ``quiet=False`` the progress line
-    comes every iteration."""
+    comes every iteration.
+
+    ``holdout`` (given like ``observed``) and ``patience`` make it a holdout
+    session (tritd_als_session_create_holdout; see ``triple_decomp_ALS``):
+    ``get()`` then also returns ``valHist``, ``best_iter`` and ``stop_reason``,
+    ``get_best()`` the factors iteration best_iter started with, and
+    ``holdout_info()`` the held-out count of the shard and ``||H o Omega o X||``.
+    ``ncvx`` with ``holdout`` is refused (TRITD_ERR_UNSUPPORTED)."""
 
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, X=None,
                  x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True, observed=None,
-                 ncvx=None):
+                 ncvx=None, holdout=None, patience=0):
         self._s = C.c_void_p()
+        self._holdout = holdout is not None
         if ncvx is not None:
             ncvx = [float(ncvx[k]) for k in ("rho", "lam", "gamma_A", "epsilon", "p", "theta")]
         o = make_als_opts(opts)
@@ -620,15 +662,25 @@ class AlsSession:
             flags |= _lib.SESSION_D_ON_DEVICE
             ldX = ldX if ldX is not None else (i1 - i0)
             optr = C.c_void_p(int(observed)) if observed is not None else None
+            hptr = C.c_void_p(int(holdout)) if holdout is not None else None
         else:
             X = _fortran(X)
             xptr = _ptr(X)
             ldX = ldX if ldX is not None else X.shape[0]
             obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
             optr = _ptr(obs)
+            hold = _observed_bytes(holdout, X.shape, "X", "holdout") if holdout is not None else None
+            hptr = _ptr(hold)
         self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
         self.maxIter = o.maxIter
-        if optr is not None:
+        if hptr is not None:
+            check(lib.tritd_als_session_create_holdout(C.byref(self._s), int(device), xptr, optr,
+                                                       hptr, int(ldX), n1, n2, n3, i0, i1, r,
+                                                       C.byref(o), int(patience), _ptr(A0),
+                                                       _ptr(B0), _ptr(C0),
+                                                       comm.handle if comm is not None else None,
+                                                       flags, int(bool(quiet))))
+        elif optr is not None:
             check(lib.tritd_als_session_create_masked(C.byref(self._s), int(device), xptr, optr,
                                                       int(ldX), n1, n2, n3, i0, i1, r, C.byref(o),
                                                       _ptr(A0), _ptr(B0), _ptr(C0),
@@ -661,6 +713,22 @@ class AlsSession:
         check(lib.tritd_als_session_mask_info(self._s, C.byref(m), C.byref(c)))
         return bool(m.value), c.value
 
+    def holdout_info(self):
+        """(held-out entries of the shard, ||H o Omega o X|| over all shards)"""
+        c, nrm = _lib.i64(0), C.c_double(0)
+        check(lib.tritd_als_session_holdout_info(self._s, C.byref(c), C.byref(nrm)))
+        return c.value, nrm.value
+
+    def get_best(self):
+        """The factors iteration best_iter started with, shaped like those of
+        ``get()``: tritd_als_session_get_best."""
+        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
+        A = np.zeros((n1, r, r), order="F")
+        B = np.zeros((r, n2, r), order="F")
+        Cf = np.zeros((r, r, n3), order="F")
+        check(lib.tritd_als_session_get_best(self._s, _ptr(A), _ptr(B), _ptr(Cf)))
+        return dict(A=A, B=B, C=Cf)
+
     def run(self, iters):
         check(lib.tritd_als_session_run(self._s, int(iters)))
 
@@ -684,7 +752,13 @@ class AlsSession:
         k = _lib.i32(0)
         check(lib.tritd_als_session_get(self._s, _ptr(A), _ptr(B), _ptr(Cf), _ptr(eh), C.byref(k)))
         _lib.warn_flags(self.flags(), "AlsSession")
-        return dict(A=A, B=B, C=Cf, errHist=eh[: k.value].copy(), k=k.value)
+        out = dict(A=A, B=B, C=Cf, errHist=eh[: k.value].copy(), k=k.value)
+        if self._holdout:
+            vh = np.zeros(max(self.maxIter, 1))
+            best, why = _lib.i32(0), _lib.i32(0)
+            check(lib.tritd_als_session_get_val(self._s, _ptr(vh), C.byref(best), C.byref(why)))
+            out.update(valHist=vh[: k.value].copy(), best_iter=best.value, stop_reason=why.value)
+        return out
 
     def set_timing(self, on=True):
         check(lib.tritd_als_session_set_timing(self._s, int(bool(on))))

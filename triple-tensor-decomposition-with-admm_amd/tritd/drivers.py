@@ -134,3 +134,43 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     return dict(A=A, B=B, C=C, O=O, errHist=errHist, X_hat=X_hat, mask=mask, rmse=rmse,
                 nrmse=nrmse, srmse=rmse2, snrmse=nrmse2, trmse=rmse3, tnrmse=nrmse3, psnr=psnr,
                 ssim=ssim, time=timer)
+
+
+def holdout_mask(observed, ratio, rng):
+    """H: `round(ratio * nnz(observed))` of the observed entries, drawn like
+    `missing_mask` (a permutation of their column-major positions)."""
+    obs = np.asarray(observed, dtype=bool)
+    idx = np.flatnonzero(obs.ravel(order="F"))
+    num = int(np.floor(ratio * idx.size + 0.5))
+    H = np.zeros(obs.size, dtype=bool)
+    H[idx[rng.permutation(idx.size)[:num]]] = True
+    return np.asfortranarray(H.reshape(obs.shape, order="F"))
+
+
+def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patience=0, *,
+                factors=None, device=-1, solver=None):
+    """Choose r by held-out validation (not in the reference): H is drawn from
+    the observed entries with a seeded generator, every candidate rank is
+    solved by `triple_decomp_ALS(observed=, holdout=H, patience=)`, and the
+    rank whose minimum valHist is smallest wins (the first on a tie).
+
+    `observed=None` means every entry.  `factors(r)` returns (A0, B0, C0) for a
+    rank (default: drawn by the solver).  Returns dict(rank=, holdout=H,
+    results={r: dict(min_val=, best_iter=, stop_reason=, k=, A=, B=, C=,
+    valHist=, errHist=)}) with A, B, C the best iterate's factors."""
+    X = np.asfortranarray(np.asarray(X, dtype=np.float64))
+    obs = np.ones(X.shape, dtype=bool) if observed is None else np.asarray(observed) != 0
+    H = holdout_mask(obs, holdout_ratio, np.random.default_rng(seed))
+    o = dict(maxIter=100, tol=1e-5) if opts is None else opts
+    solve = api.triple_decomp_ALS if solver is None else solver
+    results, chosen = {}, None
+    for r in ranks:
+        A0, B0, C0 = factors(r) if factors is not None else (None, None, None)
+        _, _, _, errHist, k, v = solve(X, r, o, A0, B0, C0, device=device, return_iters=True,
+                                       observed=obs, holdout=H, patience=patience)
+        results[r] = dict(min_val=float(v["valHist"][v["best_iter"] - 1]), best_iter=v["best_iter"],
+                          stop_reason=v["stop_reason"], k=k, A=v["A_best"], B=v["B_best"],
+                          C=v["C_best"], valHist=v["valHist"], errHist=errHist)
+        if chosen is None or results[r]["min_val"] < results[chosen]["min_val"]:
+            chosen = r
+    return dict(rank=chosen, holdout=H, results=results)
