@@ -140,6 +140,56 @@ tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int
                                    const double* B0, const double* C0, double* A, double* B,
                                    double* C, double* O, double* E, double* errHist, int32_t* iters,
                                    int32_t device);
+/* Held-out validation error, best iterate and early stopping for the masked
+ * ADMM.  `observed` (Omega; NULL = all true) and `holdout` (H) are n1*n2*n3
+ * bytes laid out like D, nonzero = true; patience >= 0; val_norm is 2 or 1.
+ * Line numbers are fast_robust_triple_tensor/triple_decomp_ADMM.m's.
+ *   Only H & Omega counts: a held-out flag at an unobserved entry is ignored,
+ *   whatever D holds there (NaN and Inf included).
+ *   The fit is exactly tritd_admm_masked_f64 with observed = Omega & ~H:
+ *   D <- (Omega & ~H) .* D, normD (:28) is that tensor's norm, and the fused
+ *   update sees the fit mask only.  With patience = 0, A, B, C, O, E, errHist
+ *   and *iters are bit for bit those of that call.  O and E are exactly 0 at
+ *   the held-out entries, as at the unobserved ones.
+ *   With L_k = triple_product(A, B, C) of the factors AFTER the updates of
+ *   iteration k (what the call would return if it ended at k):
+ *     valHist(k)  = ||H .* Omega .* (D - L_k)|| / ||H .* Omega .* D||
+ *     valHist1(k) = sum_{H & Omega} |D - L_k| / sum_{H & Omega} |D|
+ *   Both are always computed and are truncated with errHist (:68).  (The
+ *   held-out entries of a robust problem carry outliers too, and they dominate
+ *   a squared score: valHist1 is the one to read there.)  The device takes L_k
+ *   from T of iteration k+1, which the masked update leaves equal to L_k
+ *   outside the fit mask.
+ *   val_norm picks the history that drives the decisions: 2 valHist, 1 valHist1.
+ *   best_iter = argmin_k of that history, the first minimum on a tie (a strict
+ *   < against the running best, k = 1 always taken).  A_best, B_best, C_best
+ *   are the factors after iteration best_iter, kept on the device: bit for bit
+ *   the factors of the masked call with maxIter = best_iter.  O and E of the
+ *   best iterate are NOT kept (a tensor copy per improvement is too dear):
+ *   re-run the masked call with maxIter = best_iter for them.
+ *   Early stop, patience = p > 0 only: after the stop test of :63 for
+ *   iteration k, k - best_iter >= p stops the loop at k like a reference stop:
+ *   k iterations are done and the outputs are those of iteration k.
+ *   stop_reason: 0 ran to maxIter (or not stopped yet), 1 the test of :63,
+ *   2 patience.
+ *   TRITD_ERR_ARG: holdout == NULL, H & Omega empty, Omega & ~H empty,
+ *   ||H .* Omega .* D|| = 0, patience < 0, val_norm not 1 or 2.  On a device
+ *   set or with a communicator every shard refuses alike (the counts and norms
+ *   are reduced at creation).  TRITD_ERR_UNSUPPORTED: opts.model =
+ *   TRITD_MODEL_QI (and TRITD_SESSION_F32 for a session, as for any mask).
+ * valHist and valHist1 have the capacity of errHist (maxIter); A_best, B_best,
+ * C_best, valHist, valHist1, best_iter and stop_reason may be NULL.  device =
+ * -1 runs on the device set as tritd_admm_masked_f64 does (the A rows of the
+ * best iterate are shard-local, B and C replicated; every shard takes the same
+ * decisions). */
+tritd_status tritd_admm_holdout_f64(const double* D, const uint8_t* observed, const uint8_t* holdout,
+                                    int64_t n1, int64_t n2, int64_t n3, int32_t r,
+                                    const tritd_opts* opts, int32_t patience, int32_t val_norm,
+                                    const double* A0, const double* B0, const double* C0, double* A,
+                                    double* B, double* C, double* O, double* E, double* errHist,
+                                    int32_t* iters, double* A_best, double* B_best, double* C_best,
+                                    double* valHist, double* valHist1, int32_t* best_iter,
+                                    int32_t* stop_reason, int32_t device);
 
 /* ---------------------------------------------------------------------------
  * Sessions: the device-resident ADMM loop, steppable (bench), shardable
@@ -182,6 +232,39 @@ tritd_status tritd_session_create_masked(tritd_session** out, int32_t device, co
 /* Whether the session was created with a mask, and the number of observed
  * entries of its shard (all of them without a mask).  Either may be NULL. */
 tritd_status tritd_session_mask_info(tritd_session* s, int32_t* masked, int64_t* observed_count);
+/* tritd_session_create_masked with a holdout mask (tritd_admm_holdout_f64):
+ * holdout follows the conventions of observed (the mask byte of D(i0,0,0),
+ * fibres ldD BYTES apart, a device pointer exactly when
+ * TRITD_SESSION_D_ON_DEVICE is set); observed may be NULL (all true).  A run
+ * after a patience stop is a no-op, like one after a stop of :63.  With a
+ * communicator every rank creates a holdout session with the same patience
+ * and val_norm (a mismatch is TRITD_ERR_ARG on every rank). */
+tritd_status tritd_session_create_holdout(tritd_session** out, int32_t device, const void* D,
+                                          const uint8_t* observed, const uint8_t* holdout,
+                                          int64_t ldD, int64_t n1, int64_t n2, int64_t n3,
+                                          int64_t i0, int64_t i1, int32_t r, const tritd_opts* opts,
+                                          int32_t patience, int32_t val_norm, const double* A0,
+                                          const double* B0, const double* C0, tritd_comm* comm,
+                                          uint32_t flags);
+/* The held-out entries (H & Omega) of the session's shard, and
+ * ||H .* Omega .* D|| and sum |H .* Omega .* D| over all shards.  Any may be
+ * NULL. */
+tritd_status tritd_session_holdout_info(tritd_session* s, int64_t* count, double* norm,
+                                        double* sum1);
+/* valHist and valHist1 (as many entries as errHist has; capacity maxIter),
+ * best_iter (0 before the first iteration) and stop_reason.  Any may be NULL.
+ * Synchronises. */
+tritd_status tritd_session_get_val(tritd_session* s, double* valHist, double* valHist1,
+                                   int32_t* best_iter, int32_t* stop_reason);
+/* The factors after iteration best_iter (A0, B0, C0 before any run), shaped
+ * like those of tritd_session_get (A: the shard's rows).  Any may be NULL.
+ * Synchronises. */
+tritd_status tritd_session_get_best(tritd_session* s, double* A, double* B, double* C);
+/* With tritd_session_set_timing(TRITD_TIMING_ALL): ms per timed iteration in
+ * the score kernel, and from the end of the fused update to the end of the
+ * iteration (score, reductions, finish, snapshot).  Either may be NULL.
+ * These four are TRITD_ERR_STATE on a session without a holdout. */
+tritd_status tritd_session_holdout_ms(tritd_session* s, double* score_ms, double* tail_ms);
 /* Enqueue `iters` ADMM iterations (no host synchronisation unless opts.disp).
  * Iterations after the stop test of :63 fires, or beyond maxIter, are no-ops. */
 tritd_status tritd_session_run(tritd_session* s, int32_t iters);

@@ -99,6 +99,16 @@ void check_dims(int64_t n1, int64_t n2, int64_t n3, int32_t r, bool f32 = false)
     if (f32 && r > 16) throw Error(TRITD_ERR_UNSUPPORTED, "r <= 16 (R = r^2 <= 256)");
 }
 
+void need(const void* p, const char* what);
+
+// the argument rules of tritd_admm_holdout_f64 that need no device
+void check_holdout(const tritd_opts* o, int32_t patience, int32_t val_norm) {
+    if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+    if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+    if (o->model == TRITD_MODEL_QI)
+        throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not implemented for opts.model='qi'");
+}
+
 void need(const void* p, const char* what) {
     if (!p) throw Error(TRITD_ERR_ARG, std::string(what) + " is NULL");
 }
@@ -499,24 +509,43 @@ void run_threaded(DeviceGroup& grp, F&& shard) {
 // ThreadReducer.  Shard 0 runs on the calling thread, so `disp` prints (the
 // MEX's mexPrintf) stay on the host's own thread.  D, O, E are column-major
 // n1 x n2 x n3 host arrays of es-byte elements.
+// The holdout arguments of tritd_admm_holdout_f64 (every output may be null).
+struct AdmmHoldoutArgs {
+    const uint8_t* holdout;
+    int patience, val_norm;
+    double *A_best, *B_best, *C_best, *valHist, *valHist1;
+    int32_t *best_iter, *stop_reason;
+};
+
+// A rows of the best iterate are shard-local, B and C replicated; every
+// shard holds the same histories and decisions (the sums are all-reduced).
+void get_admm_holdout(Session& s, int p, const AdmmHoldoutArgs& h) {
+    int bi = 0, sr = 0;
+    s.get_val(p == 0 ? h.valHist : nullptr, p == 0 ? h.valHist1 : nullptr, &bi, &sr);
+    s.get_best(h.A_best, p == 0 ? h.B_best : nullptr, p == 0 ? h.C_best : nullptr);
+    if (p == 0 && h.best_iter) *h.best_iter = bi;
+    if (p == 0 && h.stop_reason) *h.stop_reason = sr;
+}
+
 void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags,
                       int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
                       const double* A0, const double* B0, const double* C0, double* A, double* B,
                       double* C, void* O, void* E, double* errHist, int32_t* iters,
-                      const uint8_t* observed = nullptr);
+                      const uint8_t* observed = nullptr, const AdmmHoldoutArgs* ho = nullptr);
 
 // observed (or null): the byte mask of tritd_admm_masked_f64, laid out like D
 void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags, int64_t n1,
                int64_t n2, int64_t n3, int32_t r, const tritd_opts& o, const double* A0,
                const double* B0, const double* C0, double* A, double* B, double* C, void* O,
-               void* E, double* errHist, int32_t* iters, const uint8_t* observed = nullptr) {
+               void* E, double* errHist, int32_t* iters, const uint8_t* observed = nullptr,
+               const AdmmHoldoutArgs* ho = nullptr) {
     {
         // TRITD_SHOV=0: the phase-serial order of round 1 (one host thread
         // enqueues every shard's phases, three reductions per iteration)
         const char* sh = std::getenv("TRITD_SHOV");
         if (sh && std::atoi(sh) == 0) {
             run_group_serial(devs, D, es, flags, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
-                             errHist, iters, observed);
+                             errHist, iters, observed, ho);
             return;
         }
     }
@@ -524,12 +553,14 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
     const int P = grp.size();
     if (P == 1) {
         Session s(devs[0], D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, flags, nullptr,
-                  false, observed);
+                  false, observed, ho ? ho->holdout : nullptr, ho ? ho->patience : 0,
+                  ho ? ho->val_norm : 2);
         OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * es);
         s.run(o.maxIter);
         pf.join();
         int k = 0;
         s.get(A, B, C, O, E, n1, errHist, &k, true);
+        if (ho) get_admm_holdout(s, 0, *ho);
         g_last_flags |= s.flags();
         if (iters) *iters = k;
         return;
@@ -537,12 +568,14 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
     run_threaded(grp, [&](int p, tritd_comm* comm) {
         const auto [i0, i1] = grp.rows(p, n1);
         Session s(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3, i0, i1, r, o, A0,
-                  B0, C0, comm, flags, nullptr, false, observed ? observed + i0 : nullptr);
+                  B0, C0, comm, flags, nullptr, false, observed ? observed + i0 : nullptr,
+                  ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0, ho ? ho->val_norm : 2);
         s.run(o.maxIter);
         int k = 0;
         s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
               O ? static_cast<char*>(O) + i0 * es : nullptr,
               E ? static_cast<char*>(E) + i0 * es : nullptr, n1, p == 0 ? errHist : nullptr, &k);
+        if (ho) get_admm_holdout(s, p, *ho);
         if (p == 0 && iters) *iters = k;
         return s.flags();
     });
@@ -555,7 +588,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
                       int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
                       const double* A0, const double* B0, const double* C0, double* A, double* B,
                       double* C, void* O, void* E, double* errHist, int32_t* iters,
-                      const uint8_t* observed) {
+                      const uint8_t* observed, const AdmmHoldoutArgs* ho) {
     DeviceGroup grp(devs, n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<Session>> ss;
@@ -564,10 +597,12 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new Session(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3,
                                     i0, i1, r, o, A0, B0, C0, nullptr, flags, grp.vst,
-                                    /*defer_normD=*/true, observed ? observed + i0 : nullptr));
+                                    /*defer_normD=*/true, observed ? observed + i0 : nullptr,
+                                    ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0,
+                                    ho ? ho->val_norm : 2));
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
-    grp.reduce(ss, &Session::red3, 2);
+    grp.reduce(ss, &Session::red3, ss[0]->norm_count());
     each([](Session& s) { s.set_normD_from_red3(); });
     for (int it = 0; it < o.maxIter; ++it) {
         int k = 0;
@@ -578,7 +613,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         each([&](Session& s) { s.phaseB(k); });
         grp.reduce(ss, &Session::red2, ss[0]->red2_count());
         each([&](Session& s) { s.phaseC(k); });
-        grp.reduce(ss, &Session::red3, 2);
+        grp.reduce(ss, &Session::red3, ss[0]->red3_count());
         each([&](Session& s) { s.phaseD(k); });
         TRITD_HIP(hipSetDevice(devs[0]));
         ss[0]->maybe_print(k);
@@ -590,6 +625,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         ss[p]->get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
                    O ? static_cast<char*>(O) + i0 * es : nullptr,
                    E ? static_cast<char*>(E) + i0 * es : nullptr, n1, p == 0 ? errHist : nullptr, &k);
+        if (ho) get_admm_holdout(*ss[p], p, *ho);
         g_last_flags |= ss[p]->flags();
     }
     if (iters) *iters = k;
@@ -811,6 +847,43 @@ tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int
     });
 }
 
+tritd_status tritd_admm_holdout_f64(const double* D, const uint8_t* observed, const uint8_t* holdout,
+                                    int64_t n1, int64_t n2, int64_t n3, int32_t r,
+                                    const tritd_opts* opts, int32_t patience, int32_t val_norm,
+                                    const double* A0, const double* B0, const double* C0, double* A,
+                                    double* B, double* C, double* O, double* E, double* errHist,
+                                    int32_t* iters, double* A_best, double* B_best, double* C_best,
+                                    double* valHist, double* valHist1, int32_t* best_iter,
+                                    int32_t* stop_reason, int32_t device) {
+    std::lock_guard<std::mutex> lk(g_mutex);
+    g_last_flags = 0;
+    return guarded([&] {
+        check_opts(opts);
+        check_dims(n1, n2, n3, r, true);
+        need(D, "D"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
+        check_holdout(opts, patience, val_norm);
+        const tritd_opts o = normalized(opts);
+        const AdmmHoldoutArgs ho{holdout, patience, val_norm, A_best, B_best, C_best, valHist,
+                                 valHist1, best_iter, stop_reason};
+        if (device < 0 && g_devices.size() > 1) {
+            run_group(g_devices, D, sizeof(double), 0, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
+                      errHist, iters, observed, &ho);
+            return;
+        }
+        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
+        Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, 0, nullptr, false,
+                  observed, holdout, patience, val_norm);
+        OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * sizeof(double));
+        s.run(o.maxIter);
+        pf.join();
+        int k = 0;
+        s.get(A, B, C, O, E, n1, errHist, &k, true);
+        get_admm_holdout(s, 0, ho);
+        g_last_flags |= s.flags();
+        if (iters) *iters = k;
+    });
+}
+
 tritd_status tritd_admm_f32(const float* D, int64_t n1, int64_t n2, int64_t n3, int32_t r,
                             const tritd_opts* opts, const double* A0, const double* B0,
                             const double* C0, double* A, double* B, double* C, float* O, float* E,
@@ -879,6 +952,66 @@ tritd_status tritd_session_create_masked(tritd_session** out, int32_t device, co
         auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
                               comm, flags, nullptr, false, observed);
         *out = reinterpret_cast<tritd_session*>(s);
+    });
+}
+
+tritd_status tritd_session_create_holdout(tritd_session** out, int32_t device, const void* D,
+                                          const uint8_t* observed, const uint8_t* holdout,
+                                          int64_t ldD, int64_t n1, int64_t n2, int64_t n3,
+                                          int64_t i0, int64_t i1, int32_t r, const tritd_opts* opts,
+                                          int32_t patience, int32_t val_norm, const double* A0,
+                                          const double* B0, const double* C0, tritd_comm* comm,
+                                          uint32_t flags) {
+    return guarded([&] {
+        need(out, "out");
+        *out = nullptr;
+        check_opts(opts);
+        check_dims(n1, n2, n3, r, true);
+        need(D, "D"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
+        if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
+        if (ldD < i1 - i0) throw Error(TRITD_ERR_ARG, "ldD smaller than the shard");
+        // (before any device is touched: a host without a GPU reports these too)
+        if (flags & TRITD_SESSION_F32)
+            throw Error(TRITD_ERR_UNSUPPORTED, "holdout (a mask) is implemented for a double D only");
+        check_holdout(opts, patience, val_norm);
+        const int dev = pick_device(device);
+        auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
+                              comm, flags, nullptr, false, observed, holdout, patience, val_norm);
+        *out = reinterpret_cast<tritd_session*>(s);
+    });
+}
+
+static Session* holdout_session(tritd_session* s, const char* what) {
+    need(s, "session");
+    auto* S = reinterpret_cast<Session*>(s);
+    if (!S->holdout()) throw Error(TRITD_ERR_STATE, std::string(what) + ": not a holdout session");
+    return S;
+}
+
+tritd_status tritd_session_holdout_info(tritd_session* s, int64_t* count, double* norm,
+                                        double* sum1) {
+    return guarded([&] { holdout_session(s, "holdout_info")->holdout_info(count, norm, sum1); });
+}
+
+tritd_status tritd_session_get_val(tritd_session* s, double* valHist, double* valHist1,
+                                   int32_t* best_iter, int32_t* stop_reason) {
+    return guarded([&] {
+        int bi = 0, sr = 0;
+        holdout_session(s, "get_val")->get_val(valHist, valHist1, &bi, &sr);
+        if (best_iter) *best_iter = bi;
+        if (stop_reason) *stop_reason = sr;
+    });
+}
+
+tritd_status tritd_session_get_best(tritd_session* s, double* A, double* B, double* C) {
+    return guarded([&] { holdout_session(s, "get_best")->get_best(A, B, C); });
+}
+
+tritd_status tritd_session_holdout_ms(tritd_session* s, double* score_ms, double* tail_ms) {
+    return guarded([&] {
+        Session* S = holdout_session(s, "holdout_ms");
+        S->sync(nullptr, nullptr);
+        S->holdout_ms(score_ms, tail_ms);
     });
 }
 

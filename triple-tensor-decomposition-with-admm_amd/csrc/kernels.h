@@ -221,6 +221,48 @@ void launch_mask_pack_holdout(const Geom& g, const uint8_t* obs, const uint8_t* 
 void launch_sumsq_holdout(const Geom& g, const double* X, const unsigned long long* M,
                           double* partial, int nblocks, hipStream_t st);
 void launch_soft_threshold(const double* X, int64_t n, double lam, double* Y, hipStream_t st);
+
+// ---- held-out validation of the masked ADMM (k_holdout.hip) ---
+// Packing, pass 1: obs (or null: all observed) and hold, byte masks like those
+// of launch_mask_pack -> per tile ordinal b the four fit words Omega & ~H at
+// M + MK_WORDS b (launch_mask_pack's layout: K5 and the O fix-up read them
+// unchanged), the four words of H & Omega at Hw + MK_WORDS b in the same bit
+// layout, and cnt[b] = the tile's held-out count.  Padding is fit-observed and
+// never held out.  *fit_count += |Omega & ~H| of the shard (pads excluded).
+void launch_ho_pack_words(const Geom& g, const uint8_t* obs, const uint8_t* hold, int64_t ld,
+                          unsigned long long* M, unsigned long long* Hw, unsigned* cnt,
+                          unsigned long long* fit_count, hipStream_t st);
+// hoff[b] = sum of cnt[0..b), b = 0..ntiles (hoff[ntiles] = the held-out
+// count): one workgroup, a fixed order, no atomics
+void launch_ho_scan(const unsigned* cnt, int64_t ntiles, unsigned long long* hoff, hipStream_t st);
+// Packing, pass 2: the held-out values of tile b, in the bit order of its H
+// words (word 0..3, lane 0..63 within a word), to vals + hoff[b]; D (tile-major)
+// is then zeroed wherever the fit word is clear, held-out entries included.
+void launch_ho_pack_vals(const Geom& g, const unsigned long long* M, const unsigned long long* Hw,
+                         const unsigned long long* hoff, double* D, double* vals, hipStream_t st);
+// partial[2b] = sum x^2, partial[2b + 1] = sum |x| over the n compact values
+// (ho_sum_blocks(n) pairs, a fixed traversal)
+int ho_sum_blocks(int64_t n);
+void launch_ho_valsum(const double* vals, int64_t n, double* partial, int nblocks, hipStream_t st);
+// valHist's sums after K5 of an iteration: T (TX order) holds the model value
+// at every entry outside the fit mask, so d = x - T at each held-out element;
+// partial[2b] = sum d^2, partial[2b + 1] = sum |d| (ho_score_grid(g) pairs).
+// A tile without a held-out element is skipped before any load of T.
+int ho_score_grid(const Geom& g);
+void launch_ho_score(const Geom& g, const double* T, const unsigned long long* Hw,
+                     const unsigned long long* hoff, const double* vals, double* partial,
+                     const int* stop, hipStream_t st);
+// The finish of a holdout session (one thread): finish_body (finish.h) on the
+// norm sums ss, then valHist(k) = sqrt(hs[0]) / Hnorm, valHist1(k) = hs[1] /
+// Hsum1, the running best of the history val_norm picks (a strict <, k = 1
+// always taken), the snapshot request, the patience test.  hctrl = {best_iter,
+// snapshot request, stop_reason}; best[0] = the best score so far.  An
+// iteration enqueued after a stop clears the request.
+void launch_finish_ho(const double* ss, const double* hs, double normD, double Hnorm, double Hsum1,
+                      int k, double tol, int patience, int val_norm, double* errHist, double* errL,
+                      double* errO, double* valHist, double* valHist1, int* ctrl, int* hctrl,
+                      double* best, hipStream_t st);
+
 void launch_design(char which, const double* P, const double* Q, int64_t nP, int64_t nQ, int r,
                    double* out, hipStream_t st);
 

@@ -92,13 +92,21 @@ void unpack_C(const Geom& g, const std::vector<double>& Ch, double* C) {
 Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3,
                  int64_t i0, int64_t i1, int r, const tritd_opts& o, const double* A0,
                  const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
-                 hipStream_t shared_stream, bool defer_normD, const uint8_t* observed)
-    : device_(device), o_(o), comm_(comm) {
+                 hipStream_t shared_stream, bool defer_normD, const uint8_t* observed,
+                 const uint8_t* holdout, int patience, int val_norm)
+    : device_(device), o_(o), comm_(comm), patience_(patience), val_norm_(val_norm) {
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
     f32_ = (flags & TRITD_SESSION_F32) != 0;
-    if (observed && f32_)
+    if ((observed || holdout) && f32_)
         throw Error(TRITD_ERR_UNSUPPORTED, "observed (a mask) is implemented for a double D only");
+    if (holdout) {
+        if (o_.model == TRITD_MODEL_QI)  // (the Qi K5 launch carries its own fused finish)
+            throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not implemented for opts.model='qi'");
+        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+        if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+        holdout_ = true;
+    }
     probe_ = (flags & TRITD_SESSION_PROBE) != 0;
     es_ = f32_ ? sizeof(float) : sizeof(double);
     // fp32 path and fp64 r = 9..16: padded ranks 16/32/48/64/128/256 (the
@@ -236,9 +244,10 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     }
     k5tail_ = k5n();
     if (comm_ && comm_->active()) agree_counts();
-    red1_.alloc(red1_count() + 2 * (size_t)k5tail_);  // + the tail for K5's norm partials
+    // + the tail for K5's norm partials (holdout: and the two score sums behind it)
+    red1_.alloc(red1_count() + 2 * (size_t)k5tail_ + 2);
     red2_.alloc(red2_count());
-    red3_.alloc(2);
+    red3_.alloc(8);  // 2 per iteration (holdout: 4); 5 at the creation of a holdout session
     k5part_.alloc(2 * (size_t)k5n());
     m3part_.alloc((size_t)(f32_ ? m3_parts32(g_) : m3_parts(g_)) * g_.n3p * g_.RP);
     sqpart_.alloc(2 * (size_t)sumsq_blocks(g_));
@@ -251,6 +260,19 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     const size_t ctrl_bytes = 4 * sizeof(int) + DENSE_SLOTS * sizeof(unsigned long long);
     TRITD_HIP(hipMalloc(&ctrl_, ctrl_bytes));
     TRITD_HIP(hipMemsetAsync(ctrl_, 0, ctrl_bytes, st_));
+    if (holdout_) {
+        valHist_.alloc(mi);
+        valHist1_.alloc(mi);
+        hbest_.alloc(1);
+        hopart_.alloc(2 * (size_t)ho_score_grid(g_));
+        Abest_.alloc(AhB_[0].n);
+        Bbest_.alloc(Bh_.n);
+        Cbest_.alloc(Ch_.n);
+        for (DBuf* b : {&valHist_, &valHist1_, &hbest_})
+            TRITD_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), st_));
+        TRITD_HIP(hipMalloc(&hctrl_, 4 * sizeof(int)));
+        TRITD_HIP(hipMemsetAsync(hctrl_, 0, 4 * sizeof(int), st_));
+    }
 
     // D -> tile-major device layout (one-off)
     if (g_.n1l > 0 && n2 * n3 > 0) {
@@ -269,9 +291,17 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
         }
         // D <- Omega o D and the mask words (fill values, NaN included, never
         // enter: normD below and T of iteration 1 see the zeroed D)
-        if (observed) pack_mask(observed, ldD, (flags & TRITD_SESSION_D_ON_DEVICE) != 0);
+        // (holdout: the fit mask Omega & ~H; the held-out values leave D for
+        // their compact copy before anything reads it)
+        if (observed || holdout)
+            pack_mask(observed, ldD, (flags & TRITD_SESSION_D_ON_DEVICE) != 0, holdout);
     }
     upload_factors(A0, B0, C0);
+    if (holdout_) {  // best_iter = 0 until the first iteration: A0, B0, C0
+        TRITD_HIP(hipMemcpy(Abest_.p, Ah_.p, Abest_.bytes(), hipMemcpyDeviceToDevice));
+        TRITD_HIP(hipMemcpy(Bbest_.p, Bh_.p, Bbest_.bytes(), hipMemcpyDeviceToDevice));
+        TRITD_HIP(hipMemcpy(Cbest_.p, Ch_.p, Cbest_.bytes(), hipMemcpyDeviceToDevice));
+    }
 
     // normD = norm(D(:))  (:28)
     const int nb = sumsq_blocks(g_);
@@ -280,10 +310,12 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     else
         launch_sumsq_padded(g_, D_.p, sqpart_.p, nb, st_);
     launch_reduce_pairs(sqpart_.p, nb, red3_.p, nullptr, st_);
-    if (masked_)  // the observed count rides beside normD^2 (summed over the shards)
+    if (masked_ || holdout_)  // the observed count rides beside normD^2 (summed over the shards)
         TRITD_HIP(hipMemcpyAsync(red3_.p + 1, &obs_count_d_, sizeof(double), hipMemcpyHostToDevice, st_));
+    if (holdout_)  // and ||H o Omega o D||^2, the held-out count, sum |H o Omega o D|
+        TRITD_HIP(hipMemcpyAsync(red3_.p + 2, ho_sums_, 3 * sizeof(double), hipMemcpyHostToDevice, st_));
     if (!defer_normD) {
-        allreduce(red3_.p, 2);
+        allreduce(red3_.p, norm_count());
         set_normD_from_red3();
     }
 
@@ -338,42 +370,93 @@ Session::~Session() {
         if (e) hip_quiet(hipEventDestroy(e));
     for (auto e : ev_) hip_quiet(hipEventDestroy(e));
     if (ctrl_) hip_quiet(hipFree(ctrl_));
+    if (hctrl_) hip_quiet(hipFree(hctrl_));
     if (own_stream_ && st_) hip_quiet(hipStreamDestroy(st_));
 }
 
 void Session::set_normD_from_red3() {
-    double ss[2];
-    TRITD_HIP(hipMemcpyAsync(ss, red3_.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st_));
+    double ss[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    TRITD_HIP(hipMemcpyAsync(ss, red3_.p, norm_count() * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     normD_ = std::sqrt(ss[0]);
-    if (masked_ && ss[1] == 0.0)
-        throw Error(TRITD_ERR_ARG, "observed has no true entry: nothing to fit");
+    if ((masked_ || holdout_) && ss[1] == 0.0)
+        throw Error(TRITD_ERR_ARG, holdout_ ? "no observed entry is left to fit beside the holdout"
+                                            : "observed has no true entry: nothing to fit");
+    if (holdout_) {
+        Hnorm_ = std::sqrt(ss[2]);
+        Hsum1_ = ss[4];
+        if (ss[3] == 0.0) throw Error(TRITD_ERR_ARG, "holdout has no observed entry: nothing to score");
+        if (ss[2] == 0.0) throw Error(TRITD_ERR_ARG, "the held-out entries of D are all zero");
+        // (the per-iteration sums reuse red3_[2..3])
+        TRITD_HIP(hipMemsetAsync(red3_.p, 0, red3_.bytes(), st_));
+    }
     if (f32_) normD_ = (double)(float)normD_;  // norm of a single array is single
 }
 
 // opts.observed -> M_ (and D zeroed where unobserved).  A host mask is staged
 // as a contiguous n1l x n2 x n3 byte array first.
-void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device) {
+// holdout (or null): a second byte mask of the same layout; M_ then holds the
+// fit words Omega & ~H, and Hw_, hoff_, hvals_ the held-out set (k_holdout.hip).
+void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
+                        const uint8_t* holdout) {
     masked_ = true;
-    M_.alloc_bytes((size_t)(g_.Ntm / 256) * MK_WORDS * sizeof(unsigned long long));
-    DBuf cnt, stage;
+    const int64_t ntiles = g_.Ntm / 256;
+    M_.alloc_bytes((size_t)ntiles * MK_WORDS * sizeof(unsigned long long));
+    DBuf cnt, stage, stageh;
     cnt.alloc(1);
     TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
     const uint8_t* src = observed;
+    const uint8_t* srch = holdout;
     int64_t ld = ldD;
     if (!on_device) {
         const size_t rows = (size_t)(g_.n2 * g_.n3);
-        stage.alloc_bytes((size_t)g_.n1l * rows);
-        if (ldD == g_.n1l)
-            TRITD_HIP(hipMemcpyAsync(stage.p, observed, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
-        else
-            TRITD_HIP(hipMemcpy2DAsync(stage.p, (size_t)g_.n1l, observed, (size_t)ldD, (size_t)g_.n1l,
-                                       rows, hipMemcpyHostToDevice, st_));
-        src = reinterpret_cast<const uint8_t*>(stage.p);
+        auto to_device = [&](DBuf& b, const uint8_t* m) {
+            b.alloc_bytes((size_t)g_.n1l * rows);
+            if (ldD == g_.n1l)
+                TRITD_HIP(hipMemcpyAsync(b.p, m, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
+            else
+                TRITD_HIP(hipMemcpy2DAsync(b.p, (size_t)g_.n1l, m, (size_t)ldD, (size_t)g_.n1l, rows,
+                                           hipMemcpyHostToDevice, st_));
+            return reinterpret_cast<const uint8_t*>(b.p);
+        };
+        if (observed) src = to_device(stage, observed);
+        if (holdout) srch = to_device(stageh, holdout);
         ld = g_.n1l;
     }
-    launch_mask_pack(g_, src, ld, reinterpret_cast<unsigned long long*>(M_.p), D_.p,
-                     reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    unsigned long long* M = reinterpret_cast<unsigned long long*>(M_.p);
+    if (holdout) {
+        // words and per-tile counts, the offsets by a scan, then the compact
+        // values (their number is known only after the scan) and D zeroed
+        // outside the fit mask; the two sums of the values in a fixed order
+        DBuf tcnt, vpart, vsum;
+        Hw_.alloc_bytes((size_t)ntiles * MK_WORDS * sizeof(unsigned long long));
+        hoff_.alloc((size_t)ntiles + 1);
+        tcnt.alloc_bytes((size_t)ntiles * sizeof(unsigned));
+        unsigned long long* Hw = reinterpret_cast<unsigned long long*>(Hw_.p);
+        unsigned long long* hoff = reinterpret_cast<unsigned long long*>(hoff_.p);
+        launch_ho_pack_words(g_, src, srch, ld, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
+                             reinterpret_cast<unsigned long long*>(cnt.p), st_);
+        launch_ho_scan(reinterpret_cast<const unsigned*>(tcnt.p), ntiles, hoff, st_);
+        unsigned long long nh = 0;
+        TRITD_HIP(hipMemcpyAsync(&nh, hoff + ntiles, sizeof nh, hipMemcpyDeviceToHost, st_));
+        TRITD_HIP(hipStreamSynchronize(st_));
+        ho_count_ = (int64_t)nh;
+        hvals_.alloc((size_t)nh);
+        launch_ho_pack_vals(g_, M, Hw, hoff, D_.p, hvals_.p, st_);
+        const int nb = ho_sum_blocks(ho_count_);
+        vpart.alloc(2 * (size_t)nb);
+        vsum.alloc(2);
+        launch_ho_valsum(hvals_.p, ho_count_, vpart.p, nb, st_);
+        launch_reduce_pairs(vpart.p, nb, vsum.p, nullptr, st_);
+        double hs[2] = {0.0, 0.0};
+        TRITD_HIP(hipMemcpyAsync(hs, vsum.p, sizeof hs, hipMemcpyDeviceToHost, st_));
+        TRITD_HIP(hipStreamSynchronize(st_));
+        ho_sums_[0] = hs[0];
+        ho_sums_[1] = (double)nh;
+        ho_sums_[2] = hs[1];
+    } else {
+        launch_mask_pack(g_, src, ld, M, D_.p, reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    }
     unsigned long long c = 0;
     TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
@@ -778,22 +861,26 @@ void Session::allreduce(double* buf, int64_t count) {
 // sees the same result, so a mismatch fails on all of them alike instead of
 // hanging the first collective that differs.
 void Session::agree_counts() {
-    const double c[5] = {(double)k5n(), (double)red1_count(), (double)red2_count(),
-                         (double)o_.maxIter, (double)(o_.disp != 0)};
-    double h[10];
-    for (int q = 0; q < 5; ++q) {
+    // (holdout: every rank ends its iterations alike and all-reduces two more doubles)
+    constexpr int NQ = 6;
+    const double c[NQ] = {(double)k5n(), (double)red1_count(), (double)red2_count(),
+                          (double)o_.maxIter, (double)(o_.disp != 0),
+                          holdout_ ? 1.0 + 4.0 * patience_ + val_norm_ : 0.0};
+    double h[2 * NQ];
+    for (int q = 0; q < NQ; ++q) {
         h[2 * q] = c[q];
         h[2 * q + 1] = -c[q];
     }
     DBuf v;
-    v.alloc(10);
+    v.alloc(2 * NQ);
     TRITD_HIP(hipMemcpyAsync(v.p, h, sizeof h, hipMemcpyHostToDevice, st_));
-    comm_allreduce(comm_, v.p, 10, /*max=*/true, st_);
+    comm_allreduce(comm_, v.p, 2 * NQ, /*max=*/true, st_);
     TRITD_HIP(hipMemcpyAsync(h, v.p, sizeof h, hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     k5tail_ = (int)h[0];
-    static const char* what[5] = {"", "n2 or r", "n3 or r", "opts.maxIter", "opts.disp"};
-    for (int q = 1; q < 5; ++q)
+    static const char* what[NQ] = {"", "n2 or r", "n3 or r", "opts.maxIter", "opts.disp",
+                                   "holdout, patience or val_norm"};
+    for (int q = 1; q < NQ; ++q)
         if (h[2 * q] != -h[2 * q + 1])
             throw Error(TRITD_ERR_ARG, std::string("ranks disagree on ") + what[q] +
                                            " (every rank must create its session with the same "
@@ -858,6 +945,7 @@ void Session::phaseC(int k) {
     solve(2, AtA, BtB_.p, 1e-9, GinvC_.p, st_);  // :93 ridge
     apply_gram_C();
     launch_k5_full(k, /*fused_finish=*/false);
+    if (holdout_) holdout_score(red3_.p + 2);
 }
 
 // Placement probing.  K5 is HBM-bound and its bandwidth depends on where the
@@ -1061,6 +1149,7 @@ void Session::iterate_overlapped(int k) {
     mark(4);
     norms_pending_ = true;
     pend_k_ = k;
+    if (holdout_) holdout_tail(k);
 }
 
 // Single-stream iteration (fused_): every kernel on the main stream in
@@ -1149,6 +1238,7 @@ void Session::iterate_fused(int k) {
         norms_pending_ = true;
         pend_k_ = k;
     }
+    if (holdout_) holdout_tail(k);
 }
 
 // Sharded iteration (one process per GPU).  The all-reduce
@@ -1188,11 +1278,60 @@ void Session::iterate_sharded(int k) {
     solve(0, BtB_.p, CtC_.p, o_.lambda2, GinvA_.p, side_);
     TRITD_HIP(hipEventRecord(evSA_, side_));
     launch_k5_full(k, /*fused_finish=*/false);
-    allreduce(red3_.p, 2);
+    if (holdout_) holdout_score(red3_.p + 2);
+    allreduce(red3_.p, red3_count());
     phaseD(k);
 }
 
+// The score of a holdout iteration, after its K5: T holds L_k outside the fit
+// mask.  sums[0..1] = sum d^2, sum |d| over the shard's held-out entries.
+void Session::holdout_score(double* sums) {
+    const unsigned long long* Hw = reinterpret_cast<const unsigned long long*>(Hw_.p);
+    const unsigned long long* hoff = reinterpret_cast<const unsigned long long*>(hoff_.p);
+    mark(EV_HO);
+    launch_ho_score(g_, T_.p, Hw, hoff, hvals_.p, hopart_.p, ctrl_, st_);
+    mark(EV_HO + 1);
+    launch_reduce_pairs(hopart_.p, ho_score_grid(g_), sums, ctrl_, st_);
+}
+
+// errHist(k) and the stop test of :63 as without a holdout, then the scores,
+// the running best and the patience test; the factors of iteration k are kept
+// when it is the best so far (A^ of iteration k is the current parity buffer)
+void Session::holdout_finish(int k, const double* ss, const double* hs) {
+    launch_finish_ho(ss, hs, normD_, Hnorm_, Hsum1_, k, o_.tol, patience_, val_norm_, errHist_.p,
+                     errL_.p, errO_.p, valHist_.p, valHist1_.p, ctrl_, hctrl_, hbest_.p, st_);
+    launch_als_snapshot(Ah_.p, Bh_.p, Ch_.p, Abest_.p, Bbest_.p, Cbest_.p, (int64_t)Abest_.n,
+                        (int64_t)Bbest_.n, (int64_t)Cbest_.n, hctrl_, st_);
+}
+
+// The end of a holdout iteration on the fused and overlapped schedules: the
+// norms do not pend for the next iteration's M1 / M2.  K5's partials are
+// reduced in flush_norms' order (k_reduce_pairs sums like reduce_finish_wg:
+// errHist keeps its bits); with a communicator the two score sums ride behind
+// the norm partials in red1_'s tail, in their all-reduce.
+void Session::holdout_tail(int k) {
+    if (!(comm_ && comm_->active())) {
+        holdout_score(red3_.p + 2);
+        launch_reduce_pairs(k5part_.p, k5n(), red3_.p, ctrl_, st_);
+        holdout_finish(k, red3_.p, red3_.p + 2);
+    } else {
+        double* parts = red1_.p + red1_count();
+        const size_t cnt = 2 * (size_t)k5tail_ + 2;
+        holdout_score(parts + 2 * (size_t)k5tail_);
+        allreduce(parts, (int64_t)cnt);
+        launch_reduce_pairs(parts, k5tail_, red3_.p, ctrl_, st_);
+        holdout_finish(k, red3_.p, parts + 2 * (size_t)k5tail_);
+        // (the pairs past this rank's own K5 grid must read zero next time)
+        TRITD_HIP(hipMemsetAsync(parts, 0, cnt * sizeof(double), st_));
+    }
+    norms_pending_ = false;
+}
+
 void Session::phaseD(int k) {
+    if (holdout_) {
+        holdout_finish(k, red3_.p, red3_.p + 2);
+        return;
+    }
     launch_finish(red3_.p, normD_, k, o_.tol, errHist_.p, errL_.p, errO_.p, ctrl_, f32_, st_);
 }
 
@@ -1224,7 +1363,9 @@ void Session::run(int iters) {
             const bool ar = comm_ && comm_->active();
             for (int e = 0; e < EV_SLOTS; ++e) {
                 hipEvent_t ev = nullptr;
-                if ((timing_ == TRITD_TIMING_ALL && (e < 6 || ar)) || e == 3 || e == 4)
+                const bool ho = e >= EV_HO;  // the score kernel's pair (holdout sessions)
+                if ((timing_ == TRITD_TIMING_ALL && (ho ? holdout_ : (e < 6 || ar))) || e == 3 ||
+                    e == 4)
                     TRITD_HIP(hipEventCreate(&ev));
                 ev_.push_back(ev);
             }
@@ -1245,7 +1386,7 @@ void Session::run(int iters) {
             phaseB(k);
             allreduce(red2_.p, red2_count());
             phaseC(k);
-            allreduce(red3_.p, 2);
+            allreduce(red3_.p, red3_count());
             phaseD(k);
         }
         mark(5);
@@ -1274,6 +1415,13 @@ void Session::harvest_timing() {
         }
         (void)hipGetLastError();  // an unrecorded pair is not an error
         if (nar > ar_per_iter_) ar_per_iter_ = nar;
+        if (ev_[b + EV_HO] && ev_[b + 5]) {
+            float sc = 0, tl = 0;
+            TRITD_HIP(hipEventElapsedTime(&sc, ev_[b + EV_HO], ev_[b + EV_HO + 1]));
+            TRITD_HIP(hipEventElapsedTime(&tl, ev_[b + 4], ev_[b + 5]));
+            acc_score_ += sc;
+            acc_tail_ += tl;
+        }
         acc_it_ += it;
         acc_m3_ += m3;
         acc_k5_ += k5;
@@ -1307,7 +1455,7 @@ void Session::mark(int slot) {
 
 void Session::set_timing(int level) {
     timing_ = level;
-    acc_k5_ = acc_m3_ = acc_it_ = acc_ar_ = 0;
+    acc_k5_ = acc_m3_ = acc_it_ = acc_ar_ = acc_score_ = acc_tail_ = 0;
     acc_n_ = ar_per_iter_ = 0;
 }
 
@@ -1412,6 +1560,41 @@ void Session::get(double* A, double* B, double* C, void* O, void* E, int64_t ldO
     if (errHist && done > 0)
         TRITD_HIP(hipMemcpy(errHist, errHist_.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
     if (iters) *iters = done;
+}
+
+void Session::get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason) {
+    int done = 0, stopped = 0;
+    sync(&done, &stopped);
+    if (!holdout_) throw Error(TRITD_ERR_STATE, "get_val: not a holdout session");
+    int h[3];
+    TRITD_HIP(hipMemcpy(h, hctrl_, sizeof h, hipMemcpyDeviceToHost));
+    if (valHist && done > 0)
+        TRITD_HIP(hipMemcpy(valHist, valHist_.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
+    if (valHist1 && done > 0)
+        TRITD_HIP(hipMemcpy(valHist1, valHist1_.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
+    if (best_iter) *best_iter = h[0];
+    if (stop_reason) *stop_reason = h[2];
+}
+
+void Session::get_best(double* A, double* B, double* C) {
+    int done = 0, stopped = 0;
+    sync(&done, &stopped);
+    if (!holdout_) throw Error(TRITD_ERR_STATE, "get_best: not a holdout session");
+    if (A) {
+        std::vector<double> h(Abest_.n);
+        TRITD_HIP(hipMemcpy(h.data(), Abest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unpack_A(g_, h, A);
+    }
+    if (B) {
+        std::vector<double> h(Bbest_.n);
+        TRITD_HIP(hipMemcpy(h.data(), Bbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unpack_B(g_, h, B);
+    }
+    if (C) {
+        std::vector<double> h(Cbest_.n);
+        TRITD_HIP(hipMemcpy(h.data(), Cbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+        unpack_C(g_, h, C);
+    }
 }
 
 void Session::counters(int64_t* dense_tiles_total, int64_t* tiles_per_launch) {

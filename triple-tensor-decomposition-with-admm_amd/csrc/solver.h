@@ -94,7 +94,8 @@ class Session {
     Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
             int64_t i1, int r, const tritd_opts& o, const double* A0, const double* B0,
             const double* C0, tritd_comm* comm, uint32_t flags, hipStream_t shared_stream = nullptr,
-            bool defer_normD = false, const uint8_t* observed = nullptr);
+            bool defer_normD = false, const uint8_t* observed = nullptr,
+            const uint8_t* holdout = nullptr, int patience = 0, int val_norm = 2);
     ~Session();
 
     // Enqueue iterations (full collective schedule; used without a virtual group)
@@ -122,6 +123,32 @@ class Session {
         if (masked) *masked = masked_ ? 1 : 0;
         if (observed_count) *observed_count = masked_ ? obs_count_ : g_.n1l * g_.n2 * g_.n3;
     }
+    // holdout= (tritd.h, tritd_admm_holdout_f64): the entries of
+    // H & Omega are withheld from the fit, which is the masked ADMM with
+    // observed = Omega & ~H, and scored after K5 of every iteration from T.
+    bool holdout() const { return holdout_; }
+    // held-out entries of the shard; ||H o Omega o D|| and sum |.| over all shards
+    void holdout_info(int64_t* count, double* norm, double* sum1) const {
+        if (count) *count = ho_count_;
+        if (norm) *norm = Hnorm_;
+        if (sum1) *sum1 = Hsum1_;
+    }
+    // valHist, valHist1 (as many entries as errHist), best_iter, stop_reason
+    void get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason);
+    // the factors after iteration best_iter (A0, B0, C0 before any run)
+    void get_best(double* A, double* B, double* C);
+    // ms per timed iteration (TRITD_TIMING_ALL) in the score kernel, and from
+    // the end of K5 to the end of the iteration (score, reductions, finish, snapshot)
+    void holdout_ms(double* score, double* tail) const {
+        const double n = acc_n_ ? (double)acc_n_ : 1.0;
+        if (score) *score = acc_score_ / n;
+        if (tail) *tail = acc_tail_ / n;
+    }
+    // doubles of red3 reduced over the shards at creation (normD^2, the fit
+    // count; holdout: + ||H o Omega o D||^2, the held-out count, sum |.|) and in
+    // every iteration of the phase schedules (holdout: + the two score sums)
+    int norm_count() const { return holdout_ ? 5 : 2; }
+    int red3_count() const { return holdout_ ? 4 : 2; }
     void set_timing(int level);  // 0 off, TRITD_TIMING_ALL, TRITD_TIMING_K5
     void kernel_ms(double* k5, double* m3, double* it, int* samples);
     // per timed iteration (TRITD_TIMING_ALL, with a communicator): ms inside
@@ -243,7 +270,26 @@ class Session {
     const unsigned long long* mask_words() const {
         return masked_ ? reinterpret_cast<const unsigned long long*>(M_.p) : nullptr;
     }
-    void pack_mask(const uint8_t* observed, int64_t ldD, bool on_device);
+    void pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
+                   const uint8_t* holdout = nullptr);
+    // holdout=: M_ holds the fit words Omega & ~H; Hw_ the words of H & Omega,
+    // hoff_ the tiles' offsets into hvals_, the compact held-out values
+    // (k_holdout.hip).  red3_[2..3] carry the score sums of an iteration.
+    // Control words of their own: hctrl_[0] best_iter, [1] snapshot request,
+    // [2] stop_reason; hbest_[0] = the best score so far.
+    bool holdout_ = false;
+    int patience_ = 0, val_norm_ = 2;
+    int64_t ho_count_ = 0;
+    double Hnorm_ = 0.0, Hsum1_ = 0.0;
+    double ho_sums_[3] = {0.0, 0.0, 0.0};  // creation: ||.||^2, count, sum |.| of the shard
+    int* hctrl_ = nullptr;
+    DBuf Hw_, hoff_, hvals_, hopart_, valHist_, valHist1_, hbest_, Abest_, Bbest_, Cbest_;
+    // the end of a holdout iteration: score, norm reduction, finish, snapshot
+    // (holdout_tail: the fused and overlapped schedules; the phase schedules
+    // call holdout_score after K5 and holdout_finish as their phase D)
+    void holdout_tail(int k);
+    void holdout_score(double* sums);
+    void holdout_finish(int k, const double* ss, const double* hs);
     // derived Y_O (k_admm.hip, fp64 default, TRITD_DY=0 disables): E^(k) lives
     // in compact buffer k % 2 (CE_, CE2_) and dense buffer k % 2 (E_, and the
     // pool slot of Y_O, which is not stored in this mode)
@@ -297,11 +343,12 @@ class Session {
     // per timed iteration: EV_SLOTS events — 0 start, 1/2 K2, 3/4 K5, 5 end,
     // then a (before, after) pair per all-reduce of the iteration
     static constexpr int EV_AR = 4;  // all-reduce pairs timed per iteration
-    static constexpr int EV_SLOTS = 6 + 2 * EV_AR;
+    static constexpr int EV_HO = 6 + 2 * EV_AR;  // holdout: (before, after) the score kernel
+    static constexpr int EV_SLOTS = EV_HO + 2;
     std::vector<hipEvent_t> ev_;
     std::vector<int> ev_iter_;
     int ar_in_iter_ = 0;  // all-reduces issued so far in the current iteration
-    double acc_k5_ = 0, acc_m3_ = 0, acc_it_ = 0, acc_ar_ = 0;
+    double acc_k5_ = 0, acc_m3_ = 0, acc_it_ = 0, acc_ar_ = 0, acc_score_ = 0, acc_tail_ = 0;
     int acc_n_ = 0, ar_per_iter_ = 0;
     void harvest_timing();
 };

@@ -117,6 +117,16 @@ SIGNATURES = {
                                                   i64, i64, i32, C.POINTER(Opts), vp, vp, vp, vp,
                                                   C.c_uint32, i32]),
     "tritd_als_session_mask_info": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i64)]),
+    "tritd_admm_holdout_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, C.POINTER(Opts), i32, i32, vp,
+                                         vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp, vp, vp,
+                                         vp, vp, C.POINTER(i32), C.POINTER(i32), i32]),
+    "tritd_session_create_holdout": (C.c_int, [C.POINTER(vp), i32, vp, vp, vp, i64, i64, i64, i64,
+                                               i64, i64, i32, C.POINTER(Opts), i32, i32, vp, vp, vp,
+                                               vp, C.c_uint32]),
+    "tritd_session_holdout_info": (C.c_int, [vp, C.POINTER(i64), dp, dp]),
+    "tritd_session_get_val": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+    "tritd_session_get_best": (C.c_int, [vp, vp, vp, vp]),
+    "tritd_session_holdout_ms": (C.c_int, [vp, dp, dp]),
     "tritd_als_holdout_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, C.POINTER(Opts), i32, vp, vp,
                                         vp, vp, vp, vp, vp, C.POINTER(i32), vp, vp, vp, vp,
                                         C.POINTER(i32), C.POINTER(i32), i32]),

@@ -123,7 +123,8 @@ def initial_factors(n1, n2, n3, r, opts=None, rng=None):
 
 
 def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, return_E=False,
-                       return_iters=False, virtual_shards=0, observed=None):
+                       return_iters=False, virtual_shards=0, observed=None, holdout=None,
+                       patience=0, val_norm=2):
     """[A,B,C,O,errHist] = triple_decomp_ADMM(D, r, opts) on the GPU.
 
     ``observed`` (a logical array of D's shape, True = observed) fits the
@@ -132,6 +133,20 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     errHist counts observed entries only.  float64 D; for mode-1 shards set
     the device set (``set_devices``), not ``virtual_shards``.
 
+    ``holdout`` (a logical array of D's shape; tritd_admm_holdout_f64) withholds
+    the entries of ``holdout & observed`` from the fit, which is exactly the
+    masked one with ``observed & ~holdout``, and scores them after every
+    iteration k with L_k = triple_product of the factors after its updates:
+    ``valHist(k) = ||H o Omega o (D - L_k)|| / ||H o Omega o D||`` and
+    ``valHist1(k) = sum|D - L_k| / sum|D|`` over H & Omega (the one to read when
+    the held-out entries carry outliers).  The returned tuple then gains a
+    trailing dict with ``valHist``, ``valHist1``, ``best_iter`` (the first
+    minimum of the history ``val_norm`` picks: 2 valHist, 1 valHist1),
+    ``stop_reason`` (0 maxIter, 1 the test of :63, 2 patience), ``A_best,
+    B_best, C_best`` (the factors after iteration best_iter; O and E of that
+    iterate are not kept) and ``holdout_count``.  ``patience = p > 0`` stops
+    the loop at k once ``k - best_iter >= p``.
+
     Extra outputs beyond the reference signature: E (``return_E``) and the
     iteration count (``return_iters``).  ``virtual_shards=P`` runs the mode-1
     sharded schedule as P shards on one device (rehearsal of the multi-GPU
@@ -139,7 +154,7 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     `single` D: O, E float32; A, B, C, errHist float64), r <= 16."""
     o = make_opts(opts)
     if np.asarray(D).dtype == np.float32:
-        if observed is not None:
+        if observed is not None or holdout is not None:
             raise TritdError(_lib.TRITD_ERR_UNSUPPORTED,
                              "observed (a mask) is implemented for a double D only")
         return _admm_f32(D, r, o, opts, A0, B0, C0, device, return_E, return_iters)
@@ -151,6 +166,11 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
         obs = _observed_bytes(observed, D.shape)
         if virtual_shards and virtual_shards > 1:
             raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
+    hold = None
+    if holdout is not None:
+        hold = _observed_bytes(holdout, D.shape, "D", "holdout")
+        if virtual_shards and virtual_shards > 1:
+            raise ValueError("holdout with virtual_shards: use set_devices([d] * P) and device=-1")
     if A0 is None or B0 is None or C0 is None:
         A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
     else:
@@ -163,6 +183,27 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     E = np.zeros((n1, n2, n3), order="F") if return_E else None
     errHist = np.zeros(max(o.maxIter, 1))
     k = _lib.i32(0)
+    if hold is not None:
+        Ab, Bb, Cb = np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cf)
+        valHist, valHist1 = np.zeros(max(o.maxIter, 1)), np.zeros(max(o.maxIter, 1))
+        best, why = _lib.i32(0), _lib.i32(0)
+        check_flags(lib.tritd_admm_holdout_f64(_ptr(D), _ptr(obs), _ptr(hold), n1, n2, n3, r,
+                                               C.byref(o), int(patience), int(val_norm), _ptr(A0),
+                                               _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf),
+                                               _ptr(O), _ptr(E), _ptr(errHist), C.byref(k), _ptr(Ab),
+                                               _ptr(Bb), _ptr(Cb), _ptr(valHist), _ptr(valHist1),
+                                               C.byref(best), C.byref(why), int(device)),
+                    "triple_decomp_ADMM")
+        count = int(np.count_nonzero(hold if obs is None else hold & obs))
+        out = [A, B, Cf, O, errHist[: k.value].copy()]
+        if return_E:
+            out.append(E)
+        if return_iters:
+            out.append(k.value)
+        out.append(dict(valHist=valHist[: k.value].copy(), valHist1=valHist1[: k.value].copy(),
+                        best_iter=best.value, stop_reason=why.value, A_best=Ab, B_best=Bb,
+                        C_best=Cb, holdout_count=count))
+        return tuple(out)
     if virtual_shards and virtual_shards > 1:
         check_flags(lib.tritd_admm_sharded_virtual_f64(_ptr(D), n1, n2, n3, r, C.byref(o), _ptr(A0),
                                                  _ptr(B0), _ptr(C0), int(virtual_shards), _ptr(A),
@@ -489,12 +530,21 @@ class Session:
 
     ``observed`` is the mask of the shard (tritd_session_create_masked): with
     a host D a logical array of D's shape, with ``d_device_ptr`` a device
-    pointer to bytes laid out like D (fibres ldD bytes apart).  float64 only."""
+    pointer to bytes laid out like D (fibres ldD bytes apart).  float64 only.
+
+    ``holdout`` (given like ``observed``), ``patience`` and ``val_norm`` make it
+    a holdout session (tritd_session_create_holdout; see
+    ``triple_decomp_ADMM``): ``get()`` then also returns ``valHist``,
+    ``valHist1``, ``best_iter`` and ``stop_reason`` (so does ``get_val()``,
+    without the tensors), ``get_best()`` the factors after iteration best_iter,
+    and ``holdout_info()`` the held-out count of the shard, ``||H o Omega o D||``
+    and ``sum |H o Omega o D|``."""
 
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, D=None,
                  d_device_ptr=None, ldD=None, device=0, comm=None, dtype=None, probe=True,
-                 observed=None):
+                 observed=None, holdout=None, patience=0, val_norm=2):
         self._s = C.c_void_p()
+        self._holdout = holdout is not None
         o = make_opts(opts)
         i1 = n1 if i1 is None else i1
         A0 = _fortran(A0)
@@ -512,14 +562,24 @@ class Session:
             flags |= _lib.SESSION_D_ON_DEVICE
             ldD = ldD if ldD is not None else (i1 - i0)
             optr = C.c_void_p(int(observed)) if observed is not None else None
+            hptr = C.c_void_p(int(holdout)) if holdout is not None else None
         else:
             D = np.asfortranarray(D, dtype=np.float32 if self.f32 else np.float64)
             dptr = _ptr(D)
             ldD = ldD if ldD is not None else D.shape[0]
             obs = _observed_bytes(observed, D.shape) if observed is not None else None
             optr = _ptr(obs)
+            hold = _observed_bytes(holdout, D.shape, "D", "holdout") if holdout is not None else None
+            hptr = _ptr(hold)
         self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
         self.maxIter = o.maxIter
+        if hptr is not None:
+            check(lib.tritd_session_create_holdout(C.byref(self._s), int(device), dptr, optr, hptr,
+                                                   int(ldD), n1, n2, n3, i0, i1, r, C.byref(o),
+                                                   int(patience), int(val_norm), _ptr(A0), _ptr(B0),
+                                                   _ptr(C0),
+                                                   comm.handle if comm is not None else None, flags))
+            return
         if optr is not None:
             check(lib.tritd_session_create_masked(C.byref(self._s), int(device), dptr, optr, int(ldD),
                                                   n1, n2, n3, i0, i1, r, C.byref(o), _ptr(A0),
@@ -535,6 +595,39 @@ class Session:
         m, c = _lib.i32(0), _lib.i64(0)
         check(lib.tritd_session_mask_info(self._s, C.byref(m), C.byref(c)))
         return bool(m.value), c.value
+
+    def holdout_info(self):
+        """(held-out entries of the shard, ||H o Omega o D|| and sum |H o Omega o D|
+        over all shards)"""
+        c, nrm, s1 = _lib.i64(0), C.c_double(0), C.c_double(0)
+        check(lib.tritd_session_holdout_info(self._s, C.byref(c), C.byref(nrm), C.byref(s1)))
+        return c.value, nrm.value, s1.value
+
+    def get_val(self):
+        """valHist, valHist1, best_iter, stop_reason: tritd_session_get_val."""
+        vh, vh1 = np.zeros(max(self.maxIter, 1)), np.zeros(max(self.maxIter, 1))
+        best, why = _lib.i32(0), _lib.i32(0)
+        check(lib.tritd_session_get_val(self._s, _ptr(vh), _ptr(vh1), C.byref(best), C.byref(why)))
+        k = self.sync()[0]
+        return dict(valHist=vh[:k].copy(), valHist1=vh1[:k].copy(), best_iter=best.value,
+                    stop_reason=why.value)
+
+    def get_best(self):
+        """The factors after iteration best_iter, shaped like those of ``get()``:
+        tritd_session_get_best."""
+        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
+        A = np.zeros((n1, r, r), order="F")
+        B = np.zeros((r, n2, r), order="F")
+        Cf = np.zeros((r, r, n3), order="F")
+        check(lib.tritd_session_get_best(self._s, _ptr(A), _ptr(B), _ptr(Cf)))
+        return dict(A=A, B=B, C=Cf)
+
+    def holdout_ms(self):
+        """(score kernel ms, ms from the end of K5 to the end of the iteration)
+        per timed iteration: tritd_session_holdout_ms."""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib.tritd_session_holdout_ms(self._s, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def run(self, iters):
         check(lib.tritd_session_run(self._s, int(iters)))
@@ -564,7 +657,10 @@ class Session:
         fn = lib.tritd_session_get_f32 if self.f32 else lib.tritd_session_get
         check(fn(self._s, _ptr(A), _ptr(B), _ptr(Cf), _ptr(O), _ptr(E), nl, _ptr(eh), C.byref(k)))
         _lib.warn_flags(self.flags(), "Session")
-        return dict(A=A, B=B, C=Cf, O=O, E=E, errHist=eh[: k.value].copy(), k=k.value)
+        out = dict(A=A, B=B, C=Cf, O=O, E=E, errHist=eh[: k.value].copy(), k=k.value)
+        if self._holdout:
+            out.update(self.get_val())
+        return out
 
     def rre_parts(self, dX_ptr, ldX):
         _lib.check_one_runtime("Session.rre_parts")

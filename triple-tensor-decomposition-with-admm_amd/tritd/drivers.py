@@ -148,7 +148,7 @@ def holdout_mask(observed, ratio, rng):
 
 
 def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patience=0, *,
-                factors=None, device=-1, solver=None):
+                factors=None, device=-1, solver=None, lambdas=None, val_norm=2):
     """Choose r by held-out validation (not in the reference): H is drawn from
     the observed entries with a seeded generator, every candidate rank is
     solved by `triple_decomp_ALS(observed=, holdout=H, patience=)`, and the
@@ -157,12 +157,44 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
     `observed=None` means every entry.  `factors(r)` returns (A0, B0, C0) for a
     rank (default: drawn by the solver).  Returns dict(rank=, holdout=H,
     results={r: dict(min_val=, best_iter=, stop_reason=, k=, A=, B=, C=,
-    valHist=, errHist=)}) with A, B, C the best iterate's factors."""
+    valHist=, errHist=)}) with A, B, C the best iterate's factors.
+
+    `solver` is None or "als" (the above), a callable with
+    `triple_decomp_ALS`'s signature, or "admm": the robust ADMM
+    (`triple_decomp_ADMM(observed=, holdout=H, patience=, val_norm=)`, `opts`
+    its options) over `ranks` x `lambdas` (default: the lambda of `opts`).
+    The pair whose minimum of the chosen history (`val_norm`: 2 valHist,
+    1 valHist1) is smallest wins, the first on a tie; nothing is solved again.
+    The result then also has `lam=`, `results` is keyed by (r, lambda) and its
+    entries also hold `valHist1` and `lam`."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     obs = np.ones(X.shape, dtype=bool) if observed is None else np.asarray(observed) != 0
     H = holdout_mask(obs, holdout_ratio, np.random.default_rng(seed))
+    if isinstance(solver, str) and solver not in ("als", "admm"):
+        raise ValueError("solver must be 'als', 'admm' or a callable")
+    if solver == "admm":
+        if opts is None:
+            raise ValueError("solver='admm' needs the ADMM opts")
+        lams = [api._get(opts, "lambda")] if lambdas is None else list(lambdas)
+        hist = "valHist1" if val_norm == 1 else "valHist"
+        results, chosen = {}, None
+        for r in ranks:
+            A0, B0, C0 = factors(r) if factors is not None else (None, None, None)
+            for lam in lams:
+                o = dict(opts)
+                o["lambda"] = lam
+                _, _, _, _, errHist, k, v = api.triple_decomp_ADMM(
+                    X, r, o, A0, B0, C0, device=device, return_iters=True, observed=obs, holdout=H,
+                    patience=patience, val_norm=val_norm)
+                results[(r, lam)] = dict(
+                    min_val=float(v[hist][v["best_iter"] - 1]), best_iter=v["best_iter"],
+                    stop_reason=v["stop_reason"], k=k, A=v["A_best"], B=v["B_best"], C=v["C_best"],
+                    valHist=v["valHist"], valHist1=v["valHist1"], errHist=errHist, lam=lam)
+                if chosen is None or results[(r, lam)]["min_val"] < results[chosen]["min_val"]:
+                    chosen = (r, lam)
+        return dict(rank=chosen[0], lam=chosen[1], holdout=H, results=results)
     o = dict(maxIter=100, tol=1e-5) if opts is None else opts
-    solve = api.triple_decomp_ALS if solver is None else solver
+    solve = api.triple_decomp_ALS if solver is None or solver == "als" else solver
     results, chosen = {}, None
     for r in ranks:
         A0, B0, C0 = factors(r) if factors is not None else (None, None, None)
