@@ -489,6 +489,52 @@ tritd_status tritd_ncvx_masked_f64(const double* X, const uint8_t* observed, int
                                    double tol, const double* A0, const double* B0, const double* C0,
                                    double* A, double* B, double* C, double* O, double* errHist,
                                    int32_t* iters, int32_t device);
+/* Held-out validation error, best iterate and early stopping for the masked
+ * nonconvex solver.  `observed` (Omega; NULL = all true) and `holdout` (H) are
+ * n1*n2*n3 bytes laid out like X, nonzero = true; patience >= 0; val_norm is 2
+ * or 1.  Only H & Omega counts: a held-out flag at an unobserved entry is
+ * ignored, whatever X holds there (NaN and Inf included).  Line numbers are
+ * fast_robust_triple_tensor/test.m's.
+ *   The fit is exactly tritd_ncvx_masked_f64 with observed = Omega & ~H.  With
+ *   patience = 0, A, B, C, O, errHist and *iters are bit for bit those of that
+ *   call.  O, Lambda and Gamma are exactly 0 at held-out entries, as at
+ *   unobserved ones.
+ *   With T_k the product of :35 in iteration k,
+ *     valHist(k)  = ||H .* Omega .* (X - T_k)|| / ||H .* Omega .* X||,
+ *     valHist1(k) = sum_{H & Omega} |X - T_k| / sum_{H & Omega} |X|.
+ *   Both are always computed, and truncated with errHist (:66).  They score the
+ *   factors iteration k started with.  The l1 form exists because held-out
+ *   entries of a robust problem carry outliers, which dominate the l2 form.
+ *   val_norm picks the history that drives the decisions below.
+ *   best_iter is the first minimum of that history (a strict < against the
+ *   running best, k = 1 always taken).  A_best, B_best, C_best are the factors
+ *   iteration best_iter started with (best_iter = 1: A0, B0, C0 exactly), kept
+ *   on the device; they are bit for bit the factors of the masked call run
+ *   best_iter - 1 iterations.  O of the best iterate is not kept.
+ *   Early stop, patience = p > 0 only: after the stop test of :65-68 for
+ *   iteration k, k - best_iter >= p stops the loop at k exactly like a reference
+ *   break: the updates of k have run, O is that of k-1 (:71), and both
+ *   histories have k entries.
+ *   stop_reason: 0 ran to maxIter (or not stopped yet), 1 the test of :65,
+ *   2 patience.
+ *   TRITD_ERR_ARG: holdout == NULL, H & Omega empty, Omega & ~H empty,
+ *   ||H .* Omega .* X|| = 0, patience < 0, val_norm not 1 or 2, rho == 0.  On a
+ *   device set or with a communicator every shard refuses alike (the counts and
+ *   sums are reduced at creation).  TRITD_ERR_UNSUPPORTED: r > 8.
+ * valHist and valHist1 have the capacity of errHist (maxIter); A_best, B_best,
+ * C_best, valHist, valHist1, best_iter and stop_reason may be NULL.  device = -1
+ * runs on the device set as tritd_ncvx_masked_f64 does (the A rows of the best
+ * iterate are shard-local, B and C replicated; every shard takes the same
+ * decisions because the score sums are reduced with the fit sums). */
+tritd_status tritd_ncvx_holdout_f64(const double* X, const uint8_t* observed, const uint8_t* holdout,
+                                    int64_t n1, int64_t n2, int64_t n3, int32_t r, double rho,
+                                    double lambda, double gamma_A, double epsilon, double p,
+                                    double theta, int32_t maxIter, double tol, int32_t patience,
+                                    int32_t val_norm, const double* A0, const double* B0,
+                                    const double* C0, double* A, double* B, double* C, double* O,
+                                    double* errHist, int32_t* iters, double* A_best, double* B_best,
+                                    double* C_best, double* valHist, double* valHist1,
+                                    int32_t* best_iter, int32_t* stop_reason, int32_t device);
 
 typedef struct tritd_als_session tritd_als_session;
 tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, const double* X,
@@ -518,7 +564,9 @@ tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
  * fibres ldX BYTES apart, a device pointer exactly when
  * TRITD_SESSION_D_ON_DEVICE is set); observed may be NULL (all true).  A run
  * after a patience stop is a no-op, like one after a stop of :20.
- * tritd_als_session_set_ncvx on such a session is TRITD_ERR_UNSUPPORTED. */
+ * tritd_als_session_set_ncvx on such a session is TRITD_ERR_UNSUPPORTED: this
+ * session scores inside the ALS fit kernel.  The nonconvex solver with a holdout
+ * is created by tritd_als_session_create_ncvx_holdout. */
 tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t device,
                                               const double* X, const uint8_t* observed,
                                               const uint8_t* holdout, int64_t ldX, int64_t n1,
@@ -526,6 +574,31 @@ tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t d
                                               int32_t r, const tritd_opts* opts, int32_t patience,
                                               const double* A0, const double* B0, const double* C0,
                                               tritd_comm* comm, uint32_t flags, int32_t quiet);
+/* tritd_als_session_create_holdout for the nonconvex solver
+ * (tritd_ncvx_holdout_f64): the arguments of that creator, val_norm (2 or 1)
+ * and the six positional parameters of test.m:1.  The solver is fixed at
+ * creation (tritd_als_session_set_ncvx on it is TRITD_ERR_STATE);
+ * opts->maxIter and opts->tol are the maxIter and tol of test.m.
+ * tritd_als_session_get_best, _get_O, _holdout_info and _get_val work on it;
+ * _get_val2 returns both histories.  A run after a stop of either kind is a
+ * no-op.  With a communicator every rank creates the session with the same
+ * patience, val_norm and parameters. */
+tritd_status tritd_als_session_create_ncvx_holdout(
+    tritd_als_session** out, int32_t device, const double* X, const uint8_t* observed,
+    const uint8_t* holdout, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0, int64_t i1,
+    int32_t r, const tritd_opts* opts, int32_t patience, int32_t val_norm, double rho, double lambda,
+    double gamma_A, double epsilon, double p, double theta, const double* A0, const double* B0,
+    const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet);
+/* valHist and valHist1 (as many entries as errHist has; capacity maxIter each),
+ * best_iter (0 before the first iteration) and stop_reason of a session made by
+ * tritd_als_session_create_ncvx_holdout.  Any may be NULL.  Synchronises. */
+tritd_status tritd_als_session_get_val2(tritd_als_session* s, double* valHist, double* valHist1,
+                                        int32_t* best_iter, int32_t* stop_reason);
+/* ms per timed iteration (tritd_als_session_set_timing) in the score kernel, and
+ * from the end of the fit kernel to the start of the A update (score,
+ * reductions, running best, snapshot).  Synchronises.  These two are
+ * TRITD_ERR_STATE on any other session. */
+tritd_status tritd_als_session_holdout_ms(tritd_als_session* s, double* score_ms, double* tail_ms);
 /* The held-out entries (H & Omega) of the session's shard and
  * ||H .* Omega .* X|| over all shards.  Either may be NULL. */
 tritd_status tritd_als_session_holdout_info(tritd_als_session* s, int64_t* count, double* norm);

@@ -24,13 +24,18 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
                        int64_t n3, int64_t i0, int64_t i1, int r, int maxIter, double tol,
                        const double* A0, const double* B0, const double* C0, tritd_comm* comm,
                        uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                       const uint8_t* observed, const uint8_t* holdout, int patience)
+                       const uint8_t* observed, const uint8_t* holdout, int patience,
+                       const NcvxParams* ncvx, int val_norm)
     : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm),
-      patience_(patience) {
+      patience_(patience), val_norm_(val_norm) {
     if (holdout && patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+    if (ncvx && !holdout)
+        throw Error(TRITD_ERR_ARG, "a nonconvex session without a holdout is made by enable_ncvx");
+    if (ncvx && val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+    if (ncvx && !(ncvx->rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
     try {  // (a constructor that throws runs no destructor: an all-false mask is refused here)
         init(X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, flags, shared_stream, defer_norm, observed,
-             holdout);
+             holdout, ncvx);
     } catch (...) {
         release();
         throw;
@@ -40,9 +45,10 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
 void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
                       int64_t i1, int r, const double* A0, const double* B0, const double* C0,
                       uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                      const uint8_t* observed, const uint8_t* holdout) {
+                      const uint8_t* observed, const uint8_t* holdout, const NcvxParams* ncvx) {
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
+    hoscore_ = holdout && ncvx;
     if (!rp_supported(g_.RP))
         throw Error(TRITD_ERR_UNSUPPORTED, "r must be in 1..8 for the fp64 ALS path");
     if (shared_stream) {
@@ -71,7 +77,9 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     }
     BtB_.alloc((size_t)g_.RP * g_.RP);
     CtC_.alloc((size_t)g_.RP * g_.RP);
-    red0_.alloc(4);  // 2 per iteration; 4 at the creation of a holdout session
+    // 2 per iteration (4 on a nonconvex holdout session); 4 at the creation of
+    // a holdout session (5 on a nonconvex one)
+    red0_.alloc(6);
     red1_.alloc(red1_count());
     red2_.alloc(red2_count());
     fitpart_.alloc(2 * (size_t)als_fit_grid(g_));
@@ -91,6 +99,11 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
         Cbest_.alloc(Ch_.n);
         for (DBuf* b : {&valHist_, &hbest_})
             TRITD_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), st_));
+        if (hoscore_) {
+            valHist1_.alloc(errHist_.n);
+            hopart_.alloc(2 * (size_t)ho_score_grid(g_));
+            TRITD_HIP(hipMemsetAsync(valHist1_.p, 0, valHist1_.n * sizeof(double), st_));
+        }
         TRITD_HIP(hipMalloc(&hctrl_, 4 * sizeof(int)));
         TRITD_HIP(hipMemsetAsync(hctrl_, 0, 4 * sizeof(int), st_));
     }
@@ -138,7 +151,16 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
 
     // Xnorm = norm(X(:))  (:6)
     const int nb = sumsq_blocks(g_);
-    if (holdout_) {
+    if (hoscore_) {
+        // X_ is zero outside the fit mask: the ordinary padded sum, which is how
+        // Xnorm gets the bits of the masked call on Omega & ~H.
+        // red0 = {Xnorm^2, |Omega & ~H|, ||H o Omega o X||^2, |H & Omega|, sum |H o Omega o X|}
+        launch_sumsq_padded(g_, X_.p, sqpart_.p, nb, st_);
+        launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
+        const double c[4] = {(double)obs_count_, ho_sums_[0], (double)ho_count_, ho_sums_[1]};
+        TRITD_HIP(hipMemcpyAsync(red0_.p + 1, c, sizeof c, hipMemcpyHostToDevice, st_));
+        TRITD_HIP(hipStreamSynchronize(st_));
+    } else if (holdout_) {
         // X_ holds the held-out values: the same traversal with +0 in their
         // place (bitwise the sum of the zeroed tensor), ||H o Omega o X||^2 beside it.
         // red0 = {Xnorm^2, |Omega & ~H|, ||H o Omega o X||^2, |H & Omega|}
@@ -168,6 +190,7 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     launch_gram(g_.RP, Bh_.p, g_.n2, BtB_.p, ctrl_, st_);
     launch_gram(g_.RP, Ch_.p, g_.n3p, CtC_.p, ctrl_, st_);
     TRITD_HIP(hipStreamSynchronize(st_));
+    if (ncvx) start_ncvx(*ncvx);
 }
 
 void AlsSession::release() {
@@ -186,7 +209,7 @@ void AlsSession::release() {
 AlsSession::~AlsSession() { release(); }
 
 void AlsSession::set_norm_from_red0() {
-    double ss[4] = {0.0, 0.0, 0.0, 0.0};
+    double ss[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     TRITD_HIP(hipMemcpyAsync(ss, red0_.p, norm_count() * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     Xnorm_ = std::sqrt(ss[0]);
@@ -195,6 +218,7 @@ void AlsSession::set_norm_from_red0() {
                                             : "observed has no true entry: nothing to fit");
     if (holdout_) {
         Hnorm_ = std::sqrt(ss[2]);
+        Hsum1_ = ss[4];
         if (ss[3] == 0.0) throw Error(TRITD_ERR_ARG, "holdout has no observed entry: nothing to score");
         if (ss[2] == 0.0) throw Error(TRITD_ERR_ARG, "the held-out entries of X are all zero");
     }
@@ -207,7 +231,7 @@ void AlsSession::set_norm_from_red0() {
 void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
                            const uint8_t* holdout) {
     masked_ = true;
-    M_.alloc_bytes((size_t)(g_.Ntm / 256) * (holdout ? MK_WORDS_HO : MK_WORDS) *
+    M_.alloc_bytes((size_t)(g_.Ntm / 256) * (holdout && !hoscore_ ? MK_WORDS_HO : MK_WORDS) *
                    sizeof(unsigned long long));
     DBuf cnt, stage, stageh;
     cnt.alloc(2);
@@ -230,6 +254,10 @@ void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
         if (holdout) srch = to_device(stageh, holdout);
         ld = g_.n1l;
     }
+    if (hoscore_) {
+        pack_mask_score(src, srch, ld);
+        return;
+    }
     if (holdout)
         launch_mask_pack_holdout(g_, src, srch, ld, reinterpret_cast<unsigned long long*>(M_.p),
                                  X_.p, reinterpret_cast<unsigned long long*>(cnt.p), st_);
@@ -241,6 +269,40 @@ void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
     TRITD_HIP(hipStreamSynchronize(st_));
     obs_count_ = (int64_t)c[0];
     ho_count_ = (int64_t)c[1];
+}
+
+// The nonconvex holdout form: fit words Omega & ~H into M_,
+// the held-out set into Hw_, hoff_, hvals_, X_ zeroed outside the fit words;
+// the two sums of the held-out values in a fixed order (as Session::pack_mask).
+void AlsSession::pack_mask_score(const uint8_t* src, const uint8_t* srch, int64_t ld) {
+    const int64_t ntiles = g_.Ntm / 256;
+    DBuf cnt, tcnt, vpart, vsum;
+    cnt.alloc(1);
+    TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
+    Hw_.alloc_bytes((size_t)ntiles * MK_WORDS * sizeof(unsigned long long));
+    hoff_.alloc((size_t)ntiles + 1);
+    tcnt.alloc_bytes((size_t)ntiles * sizeof(unsigned));
+    unsigned long long* M = reinterpret_cast<unsigned long long*>(M_.p);
+    unsigned long long* Hw = reinterpret_cast<unsigned long long*>(Hw_.p);
+    unsigned long long* hoff = reinterpret_cast<unsigned long long*>(hoff_.p);
+    launch_ho_pack_words(g_, src, srch, ld, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
+                         reinterpret_cast<unsigned long long*>(cnt.p), st_);
+    launch_ho_scan(reinterpret_cast<const unsigned*>(tcnt.p), ntiles, hoff, st_);
+    unsigned long long nh = 0, c = 0;
+    TRITD_HIP(hipMemcpyAsync(&nh, hoff + ntiles, sizeof nh, hipMemcpyDeviceToHost, st_));
+    TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
+    TRITD_HIP(hipStreamSynchronize(st_));
+    ho_count_ = (int64_t)nh;
+    obs_count_ = (int64_t)c;
+    hvals_.alloc((size_t)nh);
+    launch_ho_pack_vals(g_, M, Hw, hoff, X_.p, hvals_.p, st_);
+    const int nb = ho_sum_blocks(ho_count_);
+    vpart.alloc(2 * (size_t)nb);
+    vsum.alloc(2);
+    launch_ho_valsum(hvals_.p, ho_count_, vpart.p, nb, st_);
+    launch_reduce_pairs(vpart.p, nb, vsum.p, nullptr, st_);
+    TRITD_HIP(hipMemcpyAsync(ho_sums_, vsum.p, sizeof ho_sums_, hipMemcpyDeviceToHost, st_));
+    TRITD_HIP(hipStreamSynchronize(st_));
 }
 
 void AlsSession::allreduce(double* buf, int64_t count) {
@@ -259,6 +321,10 @@ void AlsSession::enable_ncvx(const NcvxParams& p) {
     if (holdout_)
         throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not supported by the nonconvex solver");
     if (!(p.rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+    start_ncvx(p);
+}
+
+void AlsSession::start_ncvx(const NcvxParams& p) {
     // (a masked session: the fit kernel runs the outlier chain on
     // X~ = where(Omega, X, T) and writes XT_ every iteration, as the masked ALS)
     TRITD_HIP(hipSetDevice(device_));
@@ -281,7 +347,7 @@ void AlsSession::phaseFit(int k) {
     if (masked_) {  // X~ = where(Omega, X, Xhat) into XT_ for this iteration's K2
         a.M = reinterpret_cast<const unsigned long long*>(M_.p);
         a.XT = XT_.p;
-        a.holdout = holdout_ ? 1 : 0;
+        a.holdout = holdout_ && !hoscore_ ? 1 : 0;
     }
     if (ncvx_) {  // test.m:35-48; O of iteration k-1 in buffer (k-1)&1, O of k into k&1
         a.ncvx = 1;
@@ -293,13 +359,33 @@ void AlsSession::phaseFit(int k) {
         a.tau = np_.lambda / np_.rho;  // lambda/rho (:44); tau.*W_O = tau (W_O = ones, :43)
         a.onep = 1.0 + np_.rho;        // (1 + rho) (:36)
     }
-    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_.size() - 5], st_));
+    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_], st_));
     launch_als_fit(g_, a, st_);
-    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_.size() - 4], st_));
+    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 1], st_));
     launch_reduce_pairs(fitpart_.p, als_fit_grid(g_), red0_.p, ctrl_, st_);
+    if (hoscore_) {
+        // XT_ holds T_k (:35) at every entry outside the fit mask; the two score
+        // sums ride behind the fit sums in the same all-reduce
+        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 5], st_));
+        launch_ho_score(g_, XT_.p, reinterpret_cast<const unsigned long long*>(Hw_.p),
+                        reinterpret_cast<const unsigned long long*>(hoff_.p), hvals_.p, hopart_.p,
+                        ctrl_, st_);
+        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 6], st_));
+        launch_reduce_pairs(hopart_.p, ho_score_grid(g_), red0_.p + 2, ctrl_, st_);
+    }
 }
 
 void AlsSession::phaseErr(int k) {
+    if (hoscore_) {
+        // both scores and the running best; the factors iteration k started
+        // with are kept, before the A update, if k is the best so far
+        launch_ncvx_ho_mark(red0_.p + 2, Hnorm_, Hsum1_, k, val_norm_, valHist_.p, valHist1_.p,
+                            ctrl_, hctrl_, hbest_.p, st_);
+        launch_als_snapshot(Ah_.p, Bh_.p, Ch_.p, Abest_.p, Bbest_.p, Cbest_.p, (int64_t)Ah_.n,
+                            (int64_t)Bh_.n, (int64_t)Ch_.n, hctrl_, st_);
+        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 7], st_));
+        return;
+    }
     if (ncvx_) return;  // test.m takes errHist after the updates: phaseEnd
     if (holdout_) {
         // valHist(k), the running best and both stop tests; then the factors
@@ -317,6 +403,10 @@ void AlsSession::phaseEnd(int k) {
     if (!ncvx_) return;
     // errHist(k) = norm(X(:) - Y_new(:) - O_new(:))/Xnorm (:62); the stop flag
     // set here makes every kernel of k+1 exit (:65-67)
+    if (hoscore_) {  // + the patience test and stop_reason
+        launch_ncvx_ho_finish(red0_.p, Xnorm_, k, tol_, patience_, errHist_.p, ctrl_, hctrl_, st_);
+        return;
+    }
     launch_als_finish(red0_.p, Xnorm_, k, tol_, errHist_.p, ctrl_, st_);
 }
 
@@ -344,9 +434,9 @@ void AlsSession::phaseB(int k) {
     launch_solve(RP, g_.R, AtA, CtC_.p, 1e-9, GinvB_.p, ctrl_ + 2, ctrl_, st_);  // :32
     launch_apply(RP, M2, g_.n2, GinvB_.p, Bh_.p, nullptr, 0, ctrl_, ctrl_ + 2, st_);
     launch_gram(RP, Bh_.p, g_.n2, BtB_.p, ctrl_, st_);
-    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_.size() - 3], st_));
+    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 2], st_));
     launch_m3(g_, XT_.p, Ah_.p, Bh_.p, m3part_.p, red2_.p, ctrl_, st_);
-    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_.size() - 2], st_));
+    if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 3], st_));
 }
 
 void AlsSession::phaseC(int k) {
@@ -378,14 +468,15 @@ void AlsSession::run(int iters) {
         const int k = next_iter();
         if (!k) break;
         if (timing_) {
-            for (int e = 0; e < 5; ++e) {
+            ev_base_ = ev_.size();
+            for (int e = 0; e < ev_slots(); ++e) {
                 hipEvent_t ev;
                 TRITD_HIP(hipEventCreate(&ev));
                 ev_.push_back(ev);
             }
         }
         phaseFit(k);
-        allreduce(red0_.p, 2);
+        allreduce(red0_.p, fit_count());
         phaseErr(k);
         if (!ncvx_) maybe_print(k);
         phaseA(k);
@@ -395,13 +486,15 @@ void AlsSession::run(int iters) {
         phaseC(k);
         phaseEnd(k);
         if (ncvx_) maybe_print(k);
-        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_.size() - 1], st_));
+        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 4], st_));
     }
 }
 
 void AlsSession::harvest_timing() {
     // events per iteration: [0] fit start, [1] fit end, [2] M3 start, [3] M3 end, [4] end
-    for (size_t b = 0; b + 5 <= ev_.size(); b += 5) {
+    // (nonconvex holdout: [5] score start, [6] score end, [7] snapshot end)
+    const size_t ns = (size_t)ev_slots();
+    for (size_t b = 0; b + ns <= ev_.size(); b += ns) {
         float it = 0, m3 = 0, fit = 0;
         TRITD_HIP(hipEventElapsedTime(&it, ev_[b], ev_[b + 4]));
         TRITD_HIP(hipEventElapsedTime(&fit, ev_[b], ev_[b + 1]));
@@ -409,6 +502,13 @@ void AlsSession::harvest_timing() {
         acc_it_ += it;
         acc_fit_ += fit;
         acc_m3_ += m3;
+        if (hoscore_) {
+            float sc = 0, tl = 0;
+            TRITD_HIP(hipEventElapsedTime(&sc, ev_[b + 5], ev_[b + 6]));
+            TRITD_HIP(hipEventElapsedTime(&tl, ev_[b + 1], ev_[b + 7]));
+            acc_score_ += sc;
+            acc_tail_ += tl;
+        }
         ++acc_n_;
     }
     for (auto e : ev_) hip_quiet(hipEventDestroy(e));
@@ -417,7 +517,7 @@ void AlsSession::harvest_timing() {
 
 void AlsSession::set_timing(bool on) {
     timing_ = on;
-    acc_fit_ = acc_m3_ = acc_it_ = 0;
+    acc_fit_ = acc_m3_ = acc_it_ = acc_score_ = acc_tail_ = 0;
     acc_n_ = 0;
 }
 
@@ -464,7 +564,7 @@ void AlsSession::get(double* A, double* B, double* C, double* errHist, int* iter
     if (iters) *iters = done;
 }
 
-void AlsSession::get_val(double* valHist, int* best_iter, int* stop_reason) {
+void AlsSession::get_val(double* valHist, int* best_iter, int* stop_reason, double* valHist1) {
     int done = 0, stopped = 0;
     sync(&done, &stopped);
     if (!holdout_) throw Error(TRITD_ERR_STATE, "get_val: not a holdout session");
@@ -472,6 +572,9 @@ void AlsSession::get_val(double* valHist, int* best_iter, int* stop_reason) {
     TRITD_HIP(hipMemcpy(h, hctrl_, sizeof h, hipMemcpyDeviceToHost));
     if (valHist && done > 0)
         TRITD_HIP(hipMemcpy(valHist, valHist_.p, (size_t)done * sizeof(double),
+                            hipMemcpyDeviceToHost));
+    if (valHist1 && hoscore_ && done > 0)
+        TRITD_HIP(hipMemcpy(valHist1, valHist1_.p, (size_t)done * sizeof(double),
                             hipMemcpyDeviceToHost));
     if (best_iter) *best_iter = h[0];
     if (stop_reason) *stop_reason = h[2];

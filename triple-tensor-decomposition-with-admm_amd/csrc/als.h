@@ -26,7 +26,7 @@ class AlsSession {
                const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
                hipStream_t shared_stream = nullptr, bool defer_norm = false,
                const uint8_t* observed = nullptr, const uint8_t* holdout = nullptr,
-               int patience = 0);
+               int patience = 0, const NcvxParams* ncvx = nullptr, int val_norm = 2);
     ~AlsSession();
     AlsSession(const AlsSession&) = delete;
     AlsSession& operator=(const AlsSession&) = delete;
@@ -63,19 +63,43 @@ class AlsSession {
     // valHist(k) = ||H o Omega o (X - Xhat)|| / ||H o Omega o X|| (tritd.h,
     // tritd_als_holdout_f64).  patience > 0 stops the loop at k when
     // k - best_iter >= patience.
+    //
+    // holdout with ncvx (the constructor's last two arguments):
+    // the nonconvex solver of test.m with the same contract
+    // (tritd_ncvx_holdout_f64).  The fit is the masked nonconvex one on
+    // Omega & ~H, untouched; it leaves the model value of every held-out
+    // entry in XT_, where k_ho_score (k_holdout.hip) reads it against a
+    // compact copy of the held-out values.  Both scores are kept: valHist
+    // (l2) and valHist1 (l1); val_norm in {2, 1} picks the one that decides.
+    // The stop tests come after the updates (test.m:62-68).
     bool holdout() const { return holdout_; }
+    bool ncvx_holdout() const { return hoscore_; }
     // held-out entries of the shard, ||H o Omega o X|| over all shards
-    void holdout_info(int64_t* count, double* norm) const {
+    // (sum1: sum |H o Omega o X|, nonconvex holdout sessions only)
+    void holdout_info(int64_t* count, double* norm, double* sum1 = nullptr) const {
         if (count) *count = ho_count_;
         if (norm) *norm = Hnorm_;
+        if (sum1) *sum1 = Hsum1_;
     }
     // valHist(1:k), best_iter, stop_reason (0 none, 1 the test of :20, 2 patience)
-    void get_val(double* valHist, int* best_iter, int* stop_reason);
+    // valHist1: the l1 history of a nonconvex holdout session (else untouched)
+    void get_val(double* valHist, int* best_iter, int* stop_reason, double* valHist1 = nullptr);
+    // nonconvex holdout sessions, timed iterations: ms in the score kernel, and
+    // from the end of the fit to the start of the A update (score, reductions,
+    // mark, snapshot)
+    void holdout_ms(double* score, double* tail) const {
+        const double n = acc_n_ ? (double)acc_n_ : 1.0;
+        if (score) *score = acc_score_ / n;
+        if (tail) *tail = acc_tail_ / n;
+    }
     // the factors iteration best_iter started with (A0, B0, C0 before any run)
     void get_best(double* A, double* B, double* C);
     // doubles of the creation-time reduction: Xnorm^2, observed count
-    // (holdout: + ||H o Omega o X||^2, held-out count)
-    int norm_count() const { return holdout_ ? 4 : 2; }
+    // (holdout: + ||H o Omega o X||^2, held-out count; nonconvex holdout: + sum |H o Omega o X|)
+    int norm_count() const { return hoscore_ ? 5 : (holdout_ ? 4 : 2); }
+    // doubles of red0 reduced after the fit: the fit sums (nonconvex holdout:
+    // + the two score sums)
+    int fit_count() const { return hoscore_ ? 4 : 2; }
     // O returned by test.m: that of iteration k-1 when the stop test broke
     // the loop at k (:67 before :71), else the last one; column-major shard
     void get_O(double* O, int64_t ldO);
@@ -117,8 +141,10 @@ class AlsSession {
     uint32_t flags_ = 0;
     int* ctrl_ = nullptr;  // [0] stop, [1] errHist entries, [2] pinv-tolerance flag
     bool timing_ = false;
-    std::vector<hipEvent_t> ev_;  // per timed iteration: 5 events
-    double acc_fit_ = 0, acc_m3_ = 0, acc_it_ = 0;
+    std::vector<hipEvent_t> ev_;  // per timed iteration: ev_slots() events
+    int ev_slots() const { return hoscore_ ? 8 : 5; }
+    size_t ev_base_ = 0;  // first event of the iteration being enqueued
+    double acc_fit_ = 0, acc_m3_ = 0, acc_it_ = 0, acc_score_ = 0, acc_tail_ = 0;
     int acc_n_ = 0;
     void harvest_timing();
     bool ncvx_ = false;
@@ -141,10 +167,21 @@ class AlsSession {
     double Hnorm_ = 0.0;
     int* hctrl_ = nullptr;
     DBuf valHist_, hbest_, Abest_, Bbest_, Cbest_;
+    // nonconvex holdout: M_ holds the four fit words per tile (Omega & ~H) the
+    // masked nonconvex fit reads, X_ is zero outside them; the held-out set
+    // lives in Hw_ (four words per tile), hoff_ (tile offsets) and hvals_
+    // (compact values), the layout of k_holdout.hip.  The score sums go to
+    // red0_[2..3] beside the fit sums.
+    bool hoscore_ = false;
+    int val_norm_ = 2;
+    double Hsum1_ = 0.0, ho_sums_[2] = {0.0, 0.0};
+    DBuf Hw_, hoff_, hvals_, hopart_, valHist1_;
+    void pack_mask_score(const uint8_t* src, const uint8_t* srch, int64_t ld);
+    void start_ncvx(const NcvxParams& p);
     void init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
               int64_t i1, int r, const double* A0, const double* B0, const double* C0,
               uint32_t flags, hipStream_t shared_stream, bool defer_norm, const uint8_t* observed,
-              const uint8_t* holdout);
+              const uint8_t* holdout, const NcvxParams* ncvx);
     void release();  // what the destructor frees beyond the members' own
 };
 

@@ -637,13 +637,16 @@ struct HoldoutArgs {
     int patience;
     double *A_best, *B_best, *C_best, *valHist;
     int32_t *best_iter, *stop_reason;
+    // tritd_ncvx_holdout_f64 only (used when the solver is the nonconvex one)
+    double* valHist1 = nullptr;
+    int val_norm = 2;
 };
 
 // A rows of the best iterate are shard-local, B and C replicated; every
 // shard holds the same valHist and decisions (the sums are all-reduced).
 void get_holdout(AlsSession& s, int p, const HoldoutArgs& h) {
     int bi = 0, sr = 0;
-    s.get_val(p == 0 ? h.valHist : nullptr, &bi, &sr);
+    s.get_val(p == 0 ? h.valHist : nullptr, &bi, &sr, p == 0 ? h.valHist1 : nullptr);
     s.get_best(h.A_best, p == 0 ? h.B_best : nullptr, p == 0 ? h.C_best : nullptr);
     if (p == 0 && h.best_iter) *h.best_iter = bi;
     if (p == 0 && h.stop_reason) *h.stop_reason = sr;
@@ -682,8 +685,8 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
         AlsSession s(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0, B0, C0,
                      grp.size() > 1 ? comm : nullptr, 0, nullptr, false,
                      observed ? observed + i0 : nullptr, ho ? ho->holdout + i0 : nullptr,
-                     ho ? ho->patience : 0);
-        if (ncvx) s.enable_ncvx(*ncvx);
+                     ho ? ho->patience : 0, ho ? ncvx : nullptr, ho ? ho->val_norm : 2);
+        if (ncvx && !ho) s.enable_ncvx(*ncvx);
         s.run(maxIter);
         int k = 0;
         s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr, p == 0 ? errHist : nullptr, &k);
@@ -708,8 +711,9 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         ss.emplace_back(new AlsSession(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0,
                                        B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true,
                                        observed ? observed + i0 : nullptr,
-                                       ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0));
-        if (ncvx) ss.back()->enable_ncvx(*ncvx);
+                                       ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0,
+                                       ho ? ncvx : nullptr, ho ? ho->val_norm : 2));
+        if (ncvx && !ho) ss.back()->enable_ncvx(*ncvx);
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
     grp.reduce(ss, &AlsSession::red0, ss[0]->norm_count());
@@ -719,7 +723,7 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         each([&](AlsSession& s) { k = s.next_iter(); });
         if (!k) break;
         each([&](AlsSession& s) { s.phaseFit(k); });
-        grp.reduce(ss, &AlsSession::red0, 2);
+        grp.reduce(ss, &AlsSession::red0, ss[0]->fit_count());
         each([&](AlsSession& s) { s.phaseErr(k); });
         TRITD_HIP(hipSetDevice(devs[0]));
         if (!ncvx) ss[0]->maybe_print(k);
@@ -1398,6 +1402,46 @@ tritd_status tritd_ncvx_masked_f64(const double* X, const uint8_t* observed, int
     });
 }
 
+tritd_status tritd_ncvx_holdout_f64(const double* X, const uint8_t* observed, const uint8_t* holdout,
+                                    int64_t n1, int64_t n2, int64_t n3, int32_t r, double rho,
+                                    double lambda, double gamma_A, double epsilon, double p,
+                                    double theta, int32_t maxIter, double tol, int32_t patience,
+                                    int32_t val_norm, const double* A0, const double* B0,
+                                    const double* C0, double* A, double* B, double* C, double* O,
+                                    double* errHist, int32_t* iters, double* A_best, double* B_best,
+                                    double* C_best, double* valHist, double* valHist1,
+                                    int32_t* best_iter, int32_t* stop_reason, int32_t device) {
+    std::lock_guard<std::mutex> lk(g_mutex);
+    g_last_flags = 0;
+    return guarded([&] {
+        check_dims(n1, n2, n3, r);
+        need(X, "X"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
+        need(A, "A"); need(B, "B"); need(C, "C"); need(O, "O"); need(errHist, "errHist");
+        if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+        if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+        const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
+        const int mi = maxIter < 0 ? 0 : maxIter;
+        const HoldoutArgs ho{holdout, patience, A_best, B_best, C_best, valHist, best_iter,
+                             stop_reason, valHist1, val_norm};
+        if (device < 0 && g_devices.size() > 1) {
+            run_als_group(g_devices, X, n1, n2, n3, r, mi, tol, A0, B0, C0, A, B, C, errHist, iters,
+                          &np, O, observed, &ho);
+            return;
+        }
+        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
+        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, mi, tol, A0, B0, C0, nullptr, 0, nullptr,
+                     false, observed, holdout, patience, &np, val_norm);
+        s.run(mi);
+        int k = 0;
+        s.get(A, B, C, errHist, &k);
+        s.get_O(O, n1);
+        get_holdout(s, 0, ho);
+        g_last_flags |= s.flags();
+        if (iters) *iters = k;
+    });
+}
+
 tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, const double* X,
                                       int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
                                       int64_t i1, int32_t r, const tritd_opts* opts,
@@ -1412,7 +1456,8 @@ static void als_session_create(tritd_als_session** out, int32_t device, const do
                         const uint8_t* observed, const uint8_t* holdout, int32_t patience,
                         int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0, int64_t i1,
                         int32_t r, const tritd_opts* opts, const double* A0, const double* B0,
-                        const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet) {
+                        const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet,
+                        const NcvxParams* ncvx = nullptr, int32_t val_norm = 2) {
     need(out, "out");
     *out = nullptr;
     check_als_opts(opts);
@@ -1425,7 +1470,7 @@ static void als_session_create(tritd_als_session** out, int32_t device, const do
     const int dev = pick_device(device);
     auto* s = new AlsSession(dev, X, ldX, n1, n2, n3, i0, i1, r,
                              opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0, comm,
-                             flags, nullptr, false, observed, holdout, patience);
+                             flags, nullptr, false, observed, holdout, patience, ncvx, val_norm);
     s->set_quiet(quiet != 0);
     *out = reinterpret_cast<tritd_als_session*>(s);
 }
@@ -1456,6 +1501,50 @@ tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t d
         if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
         als_session_create(out, device, X, observed, holdout, patience, ldX, n1, n2, n3, i0, i1, r,
                            opts, A0, B0, C0, comm, flags, quiet);
+    });
+}
+
+tritd_status tritd_als_session_create_ncvx_holdout(
+    tritd_als_session** out, int32_t device, const double* X, const uint8_t* observed,
+    const uint8_t* holdout, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0, int64_t i1,
+    int32_t r, const tritd_opts* opts, int32_t patience, int32_t val_norm, double rho, double lambda,
+    double gamma_A, double epsilon, double p, double theta, const double* A0, const double* B0,
+    const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet) {
+    return guarded([&] {
+        need(out, "out");
+        *out = nullptr;
+        need(holdout, "holdout");
+        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+        if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+        if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+        const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
+        als_session_create(out, device, X, observed, holdout, patience, ldX, n1, n2, n3, i0, i1, r,
+                           opts, A0, B0, C0, comm, flags, quiet, &np, val_norm);
+    });
+}
+
+tritd_status tritd_als_session_get_val2(tritd_als_session* s, double* valHist, double* valHist1,
+                                        int32_t* best_iter, int32_t* stop_reason) {
+    return guarded([&] {
+        need(s, "session");
+        auto* as = reinterpret_cast<AlsSession*>(s);
+        if (!as->ncvx_holdout())
+            throw Error(TRITD_ERR_STATE, "get_val2: not a nonconvex holdout session");
+        int bi = 0, sr = 0;
+        as->get_val(valHist, &bi, &sr, valHist1);
+        if (best_iter) *best_iter = bi;
+        if (stop_reason) *stop_reason = sr;
+    });
+}
+
+tritd_status tritd_als_session_holdout_ms(tritd_als_session* s, double* score_ms, double* tail_ms) {
+    return guarded([&] {
+        need(s, "session");
+        auto* as = reinterpret_cast<AlsSession*>(s);
+        if (!as->ncvx_holdout())
+            throw Error(TRITD_ERR_STATE, "holdout_ms: not a nonconvex holdout session");
+        as->sync(nullptr, nullptr);
+        as->holdout_ms(score_ms, tail_ms);
     });
 }
 

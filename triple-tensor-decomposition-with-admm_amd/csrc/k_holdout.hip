@@ -277,4 +277,67 @@ void launch_finish_ho(const double* ss, const double* hs, double normD, double H
     TRITD_CHECK_LAUNCH();
 }
 
+// Held-out validation of the masked nonconvex solver.  The
+// masked nonconvex fit stores x = fit ? X : T_k into its TX copy in every
+// iteration, so k_ho_score reads that copy exactly as it reads the ADMM's T.
+// The scores belong to the factors iteration k started with and are known
+// after the fit; errHist(k) and the stop tests come after the updates
+// (test.m:62-68).  So the finish is split in two one-thread kernels.
+//
+// After the fit of iteration k: both scores, the running best of the history
+// val_norm picks (a strict <, k = 1 always taken), the snapshot request.
+// hs = {sum d^2, sum |d|} over H & Omega, reduced over the shards.
+__global__ void k_ncvx_ho_mark(const double* hs, double Hnorm, double Hsum1, int k, int val_norm,
+                               double* valHist, double* valHist1, const int* ctrl, int* hctrl,
+                               double* best) {
+    if (ctrl[0]) {  // enqueued after a stop: nothing to keep
+        hctrl[1] = 0;
+        return;
+    }
+    const double v2 = sqrt(hs[0]) / Hnorm, v1 = hs[1] / Hsum1;
+    valHist[k - 1] = v2;
+    valHist1[k - 1] = v1;
+    const double v = val_norm == 1 ? v1 : v2;
+    int snap = 0;
+    if (k == 1 || v < best[0]) {
+        best[0] = v;
+        hctrl[0] = k;
+        snap = 1;
+    }
+    hctrl[1] = snap;
+}
+
+void launch_ncvx_ho_mark(const double* hs, double Hnorm, double Hsum1, int k, int val_norm,
+                         double* valHist, double* valHist1, const int* ctrl, int* hctrl,
+                         double* best, hipStream_t st) {
+    hipLaunchKernelGGL(k_ncvx_ho_mark, dim3(1), dim3(1), 0, st, hs, Hnorm, Hsum1, k, val_norm,
+                       valHist, valHist1, ctrl, hctrl, best);
+    TRITD_CHECK_LAUNCH();
+}
+
+// After the updates of iteration k: errHist(k) (:62), the stop test of :65,
+// then the patience test.  A stop of either kind leaves the updates of k in
+// place, like the reference's break (O stays that of k-1, :71).
+__global__ void k_ncvx_ho_finish(const double* ss, double Xnorm, int k, double tol, int patience,
+                                 double* errHist, int* ctrl, int* hctrl) {
+    if (ctrl[0]) return;
+    const double e = sqrt(ss[0]) / Xnorm;
+    errHist[k - 1] = e;
+    ctrl[1] = k;
+    if (k > 1 && fabs(e - errHist[k - 2]) < tol * errHist[k - 2]) {
+        ctrl[0] = 1;
+        hctrl[2] = 1;
+    } else if (patience > 0 && k - hctrl[0] >= patience) {
+        ctrl[0] = 1;
+        hctrl[2] = 2;
+    }
+}
+
+void launch_ncvx_ho_finish(const double* ss, double Xnorm, int k, double tol, int patience,
+                           double* errHist, int* ctrl, int* hctrl, hipStream_t st) {
+    hipLaunchKernelGGL(k_ncvx_ho_finish, dim3(1), dim3(1), 0, st, ss, Xnorm, k, tol, patience,
+                       errHist, ctrl, hctrl);
+    TRITD_CHECK_LAUNCH();
+}
+
 }  // namespace tritd

@@ -262,6 +262,18 @@ void launch_finish_ho(const double* ss, const double* hs, double normD, double H
                       int k, double tol, int patience, int val_norm, double* errHist, double* errL,
                       double* errO, double* valHist, double* valHist1, int* ctrl, int* hctrl,
                       double* best, hipStream_t st);
+// The finish of a nonconvex holdout session, in two one-thread
+// kernels.  mark, after the fit of iteration k and before its A update:
+// valHist(k) = sqrt(hs[0]) / Hnorm, valHist1(k) = hs[1] / Hsum1, the running
+// best and the snapshot request, as launch_finish_ho.  finish, after the
+// updates (test.m:62-68): errHist(k), the stop test of :65, then the patience
+// test.  ctrl, hctrl and best as above; an iteration enqueued after a stop
+// clears the request and writes nothing.
+void launch_ncvx_ho_mark(const double* hs, double Hnorm, double Hsum1, int k, int val_norm,
+                         double* valHist, double* valHist1, const int* ctrl, int* hctrl,
+                         double* best, hipStream_t st);
+void launch_ncvx_ho_finish(const double* ss, double Xnorm, int k, double tol, int patience,
+                           double* errHist, int* ctrl, int* hctrl, hipStream_t st);
 
 void launch_design(char which, const double* P, const double* Q, int64_t nP, int64_t nQ, int r,
                    double* out, hipStream_t st);

@@ -10,6 +10,7 @@ from ._lib import LIB_PATH, PinvToleranceWarning, TritdError, device_count, set_
 from .api import (  # noqa: F401
     AlsSession,
     Comm,
+    NcvxSession,
     Session,
     buildF,
     buildG,

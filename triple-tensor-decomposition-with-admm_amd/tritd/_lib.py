@@ -162,6 +162,16 @@ SIGNATURES = {
                               + [i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32),
                                  i32]),
     "tritd_als_session_set_ncvx": (C.c_int, [vp] + [C.c_double] * 6),
+    "tritd_ncvx_holdout_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32] + [C.c_double] * 6
+                               + [i32, C.c_double, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  C.POINTER(i32), vp, vp, vp, vp, vp, C.POINTER(i32),
+                                  C.POINTER(i32), i32]),
+    "tritd_als_session_create_ncvx_holdout": (C.c_int, [C.POINTER(vp), i32, vp, vp, vp, i64, i64,
+                                                        i64, i64, i64, i64, i32, C.POINTER(Opts),
+                                                        i32, i32] + [C.c_double] * 6
+                                              + [vp, vp, vp, vp, C.c_uint32, i32]),
+    "tritd_als_session_get_val2": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+    "tritd_als_session_holdout_ms": (C.c_int, [vp, dp, dp]),
     "tritd_dev_triple_product_qi_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, vp, vp]),
 }
 

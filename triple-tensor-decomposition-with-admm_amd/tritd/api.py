@@ -255,7 +255,8 @@ def _admm_f32(D, r, o, opts, A0, B0, C0, device, return_E, return_iters):
 
 # the name video_triple_comparison.m:54 calls (unresolvable in the reference)
 def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol, A0=None,
-                       B0=None, C0=None, *, device=-1, return_iters=False, observed=None):
+                       B0=None, C0=None, *, device=-1, return_iters=False, observed=None,
+                       holdout=None, patience=0, val_norm=2):
     """[A,B,C,O,errHist] of fast_robust_triple_tensor/test.m:1-73 on the GPU
     (the nonconvex variant): outlier ADMM over
     Y = X - O with duals Lambda/Gamma fused into the ALS fit kernel, the
@@ -271,12 +272,28 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
     model T, so Y = T, O is exactly 0, the duals stay 0 and errHist counts
     observed entries only, and the factor updates take where(observed, X, T)
     for X.  With every entry observed the result is the unmasked one, bit for
-    bit.  For mode-1 shards set the device set (``set_devices``)."""
+    bit.  For mode-1 shards set the device set (``set_devices``).
+
+    ``holdout`` (a logical array of X's shape; tritd_ncvx_holdout_f64) withholds
+    the entries of ``holdout & observed`` from the fit, which is exactly the
+    masked one with ``observed & ~holdout``, and scores them in every iteration
+    against T of :35: ``valHist(k) = ||H o Omega o (X - T_k)|| / ||H o Omega o X||``
+    and ``valHist1(k) = sum|H o Omega o (X - T_k)| / sum|H o Omega o X||``, for
+    the factors iteration k started with.  ``val_norm`` (2 or 1) picks the
+    history that decides.  The returned tuple then gains a trailing dict with
+    ``valHist``, ``valHist1``, ``best_iter`` (the first minimum), ``stop_reason``
+    (0 maxIter, 1 the test of :65, 2 patience), ``A_best, B_best, C_best`` (the
+    factors iteration best_iter started with; O of the best iterate is not
+    kept) and ``holdout_count``.  ``patience = p > 0`` stops the loop at k once
+    ``k - best_iter >= p``, like a break of :67."""
     X = _fortran(X)
     n1, n2, n3 = _size3(X)
     r = int(r)
     maxIter = int(maxIter)
     obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
+    hold = _observed_bytes(holdout, X.shape, "X", "holdout") if holdout is not None else None
+    if hold is None and (patience != 0 or val_norm != 2):
+        raise ValueError("patience and val_norm need holdout")
     if A0 is None or B0 is None or C0 is None:
         A0, B0, C0 = initial_factors(n1, n2, n3, r)
     else:
@@ -290,6 +307,23 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
     prm = (float(rho), float(lam), float(gamma_A), float(epsilon), float(p), float(theta), maxIter,
            float(tol), _ptr(A0), _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(O),
            _ptr(errHist), C.byref(k), int(device))
+    if hold is not None:
+        Ab, Bb, Cb = np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cf)
+        valHist, valHist1 = np.zeros(max(maxIter, 1)), np.zeros(max(maxIter, 1))
+        best, why = _lib.i32(0), _lib.i32(0)
+        check_flags(lib.tritd_ncvx_holdout_f64(_ptr(X), _ptr(obs), _ptr(hold), n1, n2, n3, r,
+                                               *prm[:8], int(patience), int(val_norm), *prm[8:17],
+                                               _ptr(Ab), _ptr(Bb), _ptr(Cb), _ptr(valHist),
+                                               _ptr(valHist1), C.byref(best), C.byref(why),
+                                               int(device)), "triple_decomp_ADMM_outlier")
+        count = int(np.count_nonzero(hold if obs is None else hold & obs))
+        out = [A, B, Cf, O, errHist[: k.value].copy()]
+        if return_iters:
+            out.append(k.value)
+        out.append(dict(valHist=valHist[: k.value].copy(), valHist1=valHist1[: k.value].copy(),
+                        best_iter=best.value, stop_reason=why.value, A_best=Ab, B_best=Bb,
+                        C_best=Cb, holdout_count=count))
+        return tuple(out)
     if obs is not None:
         check_flags(lib.tritd_ncvx_masked_f64(_ptr(X), _ptr(obs), n1, n2, n3, r, *prm),
                     "triple_decomp_ADMM_outlier")
@@ -878,6 +912,75 @@ class AlsSession:
             pass
 
 
+class NcvxSession(AlsSession):
+    """Steppable nonconvex solver of test.m:1-73 with a holdout
+    (tritd_als_session_create_ncvx_holdout; ``triple_decomp_ncvx(holdout=)``
+    stepped) on one mode-1 shard.  ``ncvx=dict(rho=, lam=, gamma_A=, epsilon=,
+    p=, theta=)``; ``opts`` carries maxIter and tol; X, ``observed`` and
+    ``holdout`` are given as for ``AlsSession`` (host arrays, or device pointers
+    with ``x_device_ptr`` and ``ldX``).  ``get()`` also returns ``valHist``,
+    ``valHist1``, ``best_iter`` and ``stop_reason`` (``get_val()`` returns those
+    alone), ``get_best()`` the factors iteration best_iter started with,
+    ``get_O()`` the shard's O, ``holdout_info()`` the held-out count of the
+    shard and ``||H o Omega o X||``, ``holdout_ms()`` the score kernel's time."""
+
+    def __init__(self, r, opts, A0, B0, C0, *, ncvx, holdout, n1, n2, n3, i0=0, i1=None, X=None,
+                 x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True, observed=None,
+                 patience=0, val_norm=2):
+        self._s = C.c_void_p()
+        self._holdout = True
+        if holdout is None:
+            raise ValueError("NcvxSession needs holdout (AlsSession(ncvx=) runs without one)")
+        prm = [float(ncvx[k]) for k in ("rho", "lam", "gamma_A", "epsilon", "p", "theta")]
+        o = make_als_opts(opts)
+        i1 = n1 if i1 is None else i1
+        A0, B0, C0 = _fortran(A0), _fortran(B0), _fortran(C0)
+        flags = 0
+        if x_device_ptr is not None:
+            xptr = C.c_void_p(int(x_device_ptr))
+            flags |= _lib.SESSION_D_ON_DEVICE
+            ldX = ldX if ldX is not None else (i1 - i0)
+            optr = C.c_void_p(int(observed)) if observed is not None else None
+            hptr = C.c_void_p(int(holdout))
+        else:
+            X = _fortran(X)
+            xptr = _ptr(X)
+            ldX = ldX if ldX is not None else X.shape[0]
+            obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
+            optr = _ptr(obs)
+            hold = _observed_bytes(holdout, X.shape, "X", "holdout")
+            hptr = _ptr(hold)
+        self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
+        self.maxIter = o.maxIter
+        check(lib.tritd_als_session_create_ncvx_holdout(
+            C.byref(self._s), int(device), xptr, optr, hptr, int(ldX), n1, n2, n3, i0, i1, r,
+            C.byref(o), int(patience), int(val_norm), *prm, _ptr(A0), _ptr(B0), _ptr(C0),
+            comm.handle if comm is not None else None, flags, int(bool(quiet))))
+
+    def get_val(self):
+        """dict(valHist, valHist1, best_iter, stop_reason): tritd_als_session_get_val2."""
+        d, _ = self.sync()
+        vh, vh1 = np.zeros(max(self.maxIter, 1)), np.zeros(max(self.maxIter, 1))
+        best, why = _lib.i32(0), _lib.i32(0)
+        check(lib.tritd_als_session_get_val2(self._s, _ptr(vh), _ptr(vh1), C.byref(best),
+                                             C.byref(why)))
+        return dict(valHist=vh[:d].copy(), valHist1=vh1[:d].copy(), best_iter=best.value,
+                    stop_reason=why.value)
+
+    def get(self):
+        out = super().get()
+        out["valHist1"] = self.get_val()["valHist1"]
+        return out
+
+    def holdout_ms(self):
+        """dict(score=, tail=): ms per timed iteration in the score kernel, and
+        from the end of the fit kernel to the start of the A update:
+        tritd_als_session_holdout_ms."""
+        a, b = C.c_double(0), C.c_double(0)
+        check(lib.tritd_als_session_holdout_ms(self._s, C.byref(a), C.byref(b)))
+        return dict(score=a.value, tail=b.value)
+
+
 class Comm:
     """RCCL communicator owned by libtritd (one process per GPU), or — with
     :meth:`host` — a host transport that hands every all-reduce to a Python
@@ -932,6 +1035,7 @@ class Comm:
 
 
 __all__ = ["triple_decomp_ADMM", "triple_decomp_ADMM_outlier", "triple_decomp_ALS", "AlsSession",
+           "NcvxSession",
            "triple_decomp_ncvx",
            "make_als_opts", "evaluate", "quality_ybz", "triple_product", "unfold",
            "soft_threshold", "buildF", "buildG", "buildH", "Session", "Comm", "TritdError",

@@ -148,7 +148,7 @@ def holdout_mask(observed, ratio, rng):
 
 
 def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patience=0, *,
-                factors=None, device=-1, solver=None, lambdas=None, val_norm=2):
+                factors=None, device=-1, solver=None, lambdas=None, val_norm=2, gammas=None):
     """Choose r by held-out validation (not in the reference): H is drawn from
     the observed entries with a seeded generator, every candidate rank is
     solved by `triple_decomp_ALS(observed=, holdout=H, patience=)`, and the
@@ -166,12 +166,48 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
     The pair whose minimum of the chosen history (`val_norm`: 2 valHist,
     1 valHist1) is smallest wins, the first on a tie; nothing is solved again.
     The result then also has `lam=`, `results` is keyed by (r, lambda) and its
-    entries also hold `valHist1` and `lam`."""
+    entries also hold `valHist1` and `lam`.
+
+    `solver="ncvx"` is the nonconvex solver of test.m
+    (`triple_decomp_ncvx(observed=, holdout=H, patience=, val_norm=)`): `opts`
+    holds its parameters `rho, lam, gamma_A, epsilon, p, theta, maxIter, tol`,
+    and the grid is `ranks` x `lambdas` x `gammas` (defaults: the `lam` and the
+    `gamma_A` of `opts`).  It is otherwise like "admm": the result also has
+    `lam=` and `gamma_A=`, and `results` is keyed by (r, lambda, gamma_A)."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     obs = np.ones(X.shape, dtype=bool) if observed is None else np.asarray(observed) != 0
     H = holdout_mask(obs, holdout_ratio, np.random.default_rng(seed))
-    if isinstance(solver, str) and solver not in ("als", "admm"):
-        raise ValueError("solver must be 'als', 'admm' or a callable")
+    if isinstance(solver, str) and solver not in ("als", "admm", "ncvx"):
+        raise ValueError("solver must be 'als', 'admm', 'ncvx' or a callable")
+    if solver == "ncvx":
+        if opts is None:
+            raise ValueError("solver='ncvx' needs the nonconvex parameters")
+        names = ("rho", "lam", "gamma_A", "epsilon", "p", "theta", "maxIter", "tol")
+        missing = [n for n in names if api._get(opts, n) is None]
+        if missing:
+            raise ValueError("solver='ncvx': opts lacks %s" % ", ".join(missing))
+        prm = {n: api._get(opts, n) for n in names}
+        lams = [prm["lam"]] if lambdas is None else list(lambdas)
+        gams = [prm["gamma_A"]] if gammas is None else list(gammas)
+        hist = "valHist1" if val_norm == 1 else "valHist"
+        results, chosen = {}, None
+        for r in ranks:
+            A0, B0, C0 = factors(r) if factors is not None else (None, None, None)
+            for lam in lams:
+                for gam in gams:
+                    _, _, _, _, errHist, k, v = api.triple_decomp_ncvx(
+                        X, r, prm["rho"], lam, gam, prm["epsilon"], prm["p"], prm["theta"],
+                        prm["maxIter"], prm["tol"], A0, B0, C0, device=device, return_iters=True,
+                        observed=obs, holdout=H, patience=patience, val_norm=val_norm)
+                    key = (r, lam, gam)
+                    results[key] = dict(
+                        min_val=float(v[hist][v["best_iter"] - 1]), best_iter=v["best_iter"],
+                        stop_reason=v["stop_reason"], k=k, A=v["A_best"], B=v["B_best"],
+                        C=v["C_best"], valHist=v["valHist"], valHist1=v["valHist1"],
+                        errHist=errHist, lam=lam, gamma_A=gam)
+                    if chosen is None or results[key]["min_val"] < results[chosen]["min_val"]:
+                        chosen = key
+        return dict(rank=chosen[0], lam=chosen[1], gamma_A=chosen[2], holdout=H, results=results)
     if solver == "admm":
         if opts is None:
             raise ValueError("solver='admm' needs the ADMM opts")
