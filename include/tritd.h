@@ -134,7 +134,18 @@ tritd_status tritd_admm_f32(const float* D, int64_t n1, int64_t n2, int64_t n3, 
  * there, and errHist counts observed entries only.  observed == NULL behaves
  * as tritd_admm_f64; a mask with no true entry is TRITD_ERR_ARG.  device = -1
  * runs on the device set (mode-1 shards, one device repeated P times
- * included).  opts.model = TRITD_MODEL_QI is supported. */
+ * included).  opts.model = TRITD_MODEL_QI is supported.
+ *   NaN as missing: observed = TRITD_OBSERVED_NAN (below) means
+ *   Omega = ~isnan(D), elementwise, and no mask array exists.  Any NaN counts
+ *   as missing (either sign, any payload, quiet or signalling); +-Inf is data.
+ *   The mask is taken from D on the device; every output is bit for bit that
+ *   of the same call with the byte mask (uint8_t)!isnan(D).  Every `observed`
+ *   parameter of this header accepts the constant, the holdout forms and the
+ *   session creators (device-resident D, any leading dimension) included; a
+ *   `holdout` array stays a byte mask.  The constant is never dereferenced and
+ *   never offset (shards pass it through).  An all-NaN D is the mask with no
+ *   true entry.  Without the constant a NaN in D is data and propagates. */
+#define TRITD_OBSERVED_NAN ((const uint8_t*)(uintptr_t)1)
 tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int64_t n1, int64_t n2,
                                    int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
                                    const double* B0, const double* C0, double* A, double* B,
@@ -143,6 +154,7 @@ tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int
 /* Held-out validation error, best iterate and early stopping for the masked
  * ADMM.  `observed` (Omega; NULL = all true) and `holdout` (H) are n1*n2*n3
  * bytes laid out like D, nonzero = true; patience >= 0; val_norm is 2 or 1.
+ * observed may be TRITD_OBSERVED_NAN (tritd_admm_masked_f64).
  * Line numbers are fast_robust_triple_tensor/triple_decomp_ADMM.m's.
  *   Only H & Omega counts: a held-out flag at an unobserved entry is ignored,
  *   whatever D holds there (NaN and Inf included).
@@ -223,7 +235,8 @@ tritd_status tritd_session_create(tritd_session** out, int32_t device, const voi
  * element).  It is a device pointer exactly when TRITD_SESSION_D_ON_DEVICE is
  * set.  observed == NULL: as tritd_session_create.  With TRITD_SESSION_F32 a
  * mask is TRITD_ERR_UNSUPPORTED; a mask with no true entry in any shard is
- * TRITD_ERR_ARG (with a communicator: on every rank alike). */
+ * TRITD_ERR_ARG (with a communicator: on every rank alike).  observed may be
+ * TRITD_OBSERVED_NAN (tritd_admm_masked_f64), with a host or a device D. */
 tritd_status tritd_session_create_masked(tritd_session** out, int32_t device, const void* D,
                                          const uint8_t* observed, int64_t ldD, int64_t n1,
                                          int64_t n2, int64_t n3, int64_t i0, int64_t i1, int32_t r,

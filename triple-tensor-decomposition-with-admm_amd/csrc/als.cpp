@@ -250,7 +250,7 @@ void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
                                            hipMemcpyHostToDevice, st_));
             return reinterpret_cast<const uint8_t*>(b.p);
         };
-        if (observed) src = to_device(stage, observed);
+        if (observed && !obs_is_nan(observed)) src = to_device(stage, observed);
         if (holdout) srch = to_device(stageh, holdout);
         ld = g_.n1l;
     }
@@ -285,7 +285,7 @@ void AlsSession::pack_mask_score(const uint8_t* src, const uint8_t* srch, int64_
     unsigned long long* M = reinterpret_cast<unsigned long long*>(M_.p);
     unsigned long long* Hw = reinterpret_cast<unsigned long long*>(Hw_.p);
     unsigned long long* hoff = reinterpret_cast<unsigned long long*>(hoff_.p);
-    launch_ho_pack_words(g_, src, srch, ld, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
+    launch_ho_pack_words(g_, src, srch, ld, X_.p, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
                          reinterpret_cast<unsigned long long*>(cnt.p), st_);
     launch_ho_scan(reinterpret_cast<const unsigned*>(tcnt.p), ntiles, hoff, st_);
     unsigned long long nh = 0, c = 0;

@@ -568,7 +568,7 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
     run_threaded(grp, [&](int p, tritd_comm* comm) {
         const auto [i0, i1] = grp.rows(p, n1);
         Session s(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3, i0, i1, r, o, A0,
-                  B0, C0, comm, flags, nullptr, false, observed ? observed + i0 : nullptr,
+                  B0, C0, comm, flags, nullptr, false, obs_rows(observed, i0),
                   ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0, ho ? ho->val_norm : 2);
         s.run(o.maxIter);
         int k = 0;
@@ -597,7 +597,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new Session(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3,
                                     i0, i1, r, o, A0, B0, C0, nullptr, flags, grp.vst,
-                                    /*defer_normD=*/true, observed ? observed + i0 : nullptr,
+                                    /*defer_normD=*/true, obs_rows(observed, i0),
                                     ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0,
                                     ho ? ho->val_norm : 2));
     }
@@ -684,7 +684,7 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
         const auto [i0, i1] = grp.rows(p, n1);
         AlsSession s(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0, B0, C0,
                      grp.size() > 1 ? comm : nullptr, 0, nullptr, false,
-                     observed ? observed + i0 : nullptr, ho ? ho->holdout + i0 : nullptr,
+                     obs_rows(observed, i0), ho ? ho->holdout + i0 : nullptr,
                      ho ? ho->patience : 0, ho ? ncvx : nullptr, ho ? ho->val_norm : 2);
         if (ncvx && !ho) s.enable_ncvx(*ncvx);
         s.run(maxIter);
@@ -710,7 +710,7 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new AlsSession(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0,
                                        B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true,
-                                       observed ? observed + i0 : nullptr,
+                                       obs_rows(observed, i0),
                                        ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0,
                                        ho ? ncvx : nullptr, ho ? ho->val_norm : 2));
         if (ncvx && !ho) ss.back()->enable_ncvx(*ncvx);

@@ -158,6 +158,22 @@ constexpr int MK_WORDS = 4;
 // words 0-3 as above for the fit mask Omega & ~H, words 4-7 for H & Omega.
 constexpr int MK_WORDS_HO = 8;
 
+// TRITD_OBSERVED_NAN (tritd.h): Omega = ~isnan(D), taken from the tile-major
+// tensor by the packing kernels.  The constant is compared,
+// never dereferenced and never offset.
+inline bool obs_is_nan(const uint8_t* observed) { return observed == TRITD_OBSERVED_NAN; }
+// the mask pointer of the shard that starts at row i0
+inline const uint8_t* obs_rows(const uint8_t* observed, int64_t i0) {
+    return !observed || obs_is_nan(observed) ? observed : observed + i0;
+}
+// Any NaN (either sign, any payload, quiet or signalling), by its bits: the
+// answer does not depend on how the compiler treats floating compares.
+__host__ __device__ inline bool is_nan_bits(double x) {
+    unsigned long long u;
+    __builtin_memcpy(&u, &x, sizeof u);
+    return (u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+
 __host__ __device__ inline int64_t tm_tile_base(int64_t g, int64_t tt, int64_t ntt) {
     return ((((g >> 2) * ntt + tt) << 2) + (g & 3)) << 8;
 }

@@ -20,11 +20,15 @@ namespace tritd {
 
 typedef double d2v __attribute__((ext_vector_type(2)));
 
+// NANM (TRITD_OBSERVED_NAN): the observed bit is !isnan of the
+// lane's own element of the tile-major D (read only here: k_ho_pack_vals
+// zeroes it afterwards), obs is not read.
+template <bool NANM>
 __global__ __launch_bounds__(256) void k_ho_pack_words(
     const uint8_t* __restrict__ obs, const uint8_t* __restrict__ hold, int64_t ld, int64_t n1l,
     int64_t n2, int64_t n3, int64_t n1p, int64_t ntt, int64_t ntiles,
-    unsigned long long* __restrict__ M, unsigned long long* __restrict__ Hw,
-    unsigned* __restrict__ cnt, unsigned long long* fit_count) {
+    const double* __restrict__ D, unsigned long long* __restrict__ M,
+    unsigned long long* __restrict__ Hw, unsigned* __restrict__ cnt, unsigned long long* fit_count) {
     const int l = threadIdx.x & 63;
     const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // tile ordinal
     if (blk >= ntiles) return;
@@ -38,7 +42,11 @@ __global__ __launch_bounds__(256) void k_ho_pack_words(
         const int64_t t = 16 * tt + (l >> 4) + 4 * w;
         const bool real = i < n1l && j < n2 && t < n3;
         const int64_t o = real ? (t * n2 + j) * ld + i : 0;
-        const bool on = !real || !obs || obs[o] != 0;
+        bool on;
+        if constexpr (NANM)
+            on = !real || !is_nan_bits(D[(blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1)]);
+        else
+            on = !real || !obs || obs[o] != 0;
         const bool ho = real && on && hold[o] != 0;  // a flag outside Omega is ignored
         const unsigned long long fw = __ballot(on && !ho), hw = __ballot(ho);
         fitn += __builtin_popcountll(__ballot(real && on && !ho));
@@ -53,11 +61,16 @@ __global__ __launch_bounds__(256) void k_ho_pack_words(
 }
 
 void launch_ho_pack_words(const Geom& g, const uint8_t* obs, const uint8_t* hold, int64_t ld,
-                          unsigned long long* M, unsigned long long* Hw, unsigned* cnt,
-                          unsigned long long* fit_count, hipStream_t st) {
+                          const double* D, unsigned long long* M, unsigned long long* Hw,
+                          unsigned* cnt, unsigned long long* fit_count, hipStream_t st) {
     const int64_t ntiles = g.Ntm / 256;
-    hipLaunchKernelGGL(k_ho_pack_words, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, st, obs, hold,
-                       ld, g.n1l, g.n2, g.n3, g.n1p, g.ntt, ntiles, M, Hw, cnt, fit_count);
+    const dim3 grid((unsigned)cdiv(ntiles, 4)), block(256);
+    if (obs_is_nan(obs))
+        hipLaunchKernelGGL(k_ho_pack_words<true>, grid, block, 0, st, nullptr, hold, ld, g.n1l, g.n2,
+                           g.n3, g.n1p, g.ntt, ntiles, D, M, Hw, cnt, fit_count);
+    else
+        hipLaunchKernelGGL(k_ho_pack_words<false>, grid, block, 0, st, obs, hold, ld, g.n1l, g.n2,
+                           g.n3, g.n1p, g.ntt, ntiles, D, M, Hw, cnt, fit_count);
     TRITD_CHECK_LAUNCH();
 }
 

@@ -711,6 +711,10 @@ void launch_to_tm(const Geom& g, const double* src, int64_t ld, double* dst, hip
 // ballots are the words; an unobserved element of D (TM position
 // (w>>1)*128 + 2l + (w&1)) is zeroed, so a fill value never enters the solve;
 // the observed entries of the shard itself are counted (one atomic per wave).
+// NANM (TRITD_OBSERVED_NAN): the observed bit comes from the
+// tensor, not from obs: the lane tests the element it would zero, in the
+// tile-major D that launch_to_tm has just written.
+template <bool NANM>
 __global__ __launch_bounds__(256) void k_mask_pack(const uint8_t* __restrict__ obs, int64_t ld,
                                                    int64_t n1l, int64_t n2, int64_t n3,
                                                    int64_t n1p, int64_t ntt, int64_t ntiles,
@@ -729,11 +733,16 @@ __global__ __launch_bounds__(256) void k_mask_pack(const uint8_t* __restrict__ o
     for (int w = 0; w < MK_WORDS; ++w) {
         const int64_t t = 16 * tt + (l >> 4) + 4 * w;
         const bool real = i < n1l && j < n2 && t < n3;
-        const bool on = !real || obs[(t * n2 + j) * ld + i] != 0;
+        const int64_t e = (blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1);
+        bool on;
+        if constexpr (NANM)
+            on = !real || !is_nan_bits(D[e]);
+        else
+            on = !real || obs[(t * n2 + j) * ld + i] != 0;
         const unsigned long long word = __ballot(on);
         seen += __builtin_popcountll(__ballot(real && on));
         if (l == w) M[blk * MK_WORDS + w] = word;
-        if (!on) D[(blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1)] = 0.0;
+        if (!on) D[e] = 0.0;
     }
     if (l == 0 && seen) atomicAdd(count, (unsigned long long)seen);
 }
@@ -741,15 +750,21 @@ __global__ __launch_bounds__(256) void k_mask_pack(const uint8_t* __restrict__ o
 void launch_mask_pack(const Geom& g, const uint8_t* obs, int64_t ld, unsigned long long* M,
                       double* D, unsigned long long* count, hipStream_t st) {
     const int64_t ntiles = g.Ntm / 256;
-    hipLaunchKernelGGL(k_mask_pack, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, st, obs, ld,
-                       g.n1l, g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
+    const dim3 grid((unsigned)cdiv(ntiles, 4)), block(256);
+    if (obs_is_nan(obs))
+        hipLaunchKernelGGL(k_mask_pack<true>, grid, block, 0, st, nullptr, ld, g.n1l, g.n2, g.n3,
+                           g.n1p, g.ntt, ntiles, M, D, count);
+    else
+        hipLaunchKernelGGL(k_mask_pack<false>, grid, block, 0, st, obs, ld, g.n1l, g.n2, g.n3,
+                           g.n1p, g.ntt, ntiles, M, D, count);
     TRITD_CHECK_LAUNCH();
 }
 
 // k_mask_pack for a holdout session: obs (null: all observed) and hold -> eight
 // words per tile, 0-3 the fit mask Omega & ~H, 4-7 H & Omega.  D is zeroed only
 // where unobserved (a held-out value stays for valHist); padding is
-// fit-observed and never held out; both sets are counted.
+// fit-observed and never held out; both sets are counted.  NANM: as k_mask_pack.
+template <bool NANM>
 __global__ __launch_bounds__(256) void k_mask_pack_holdout(
     const uint8_t* __restrict__ obs, const uint8_t* __restrict__ hold, int64_t ld, int64_t n1l,
     int64_t n2, int64_t n3, int64_t n1p, int64_t ntt, int64_t ntiles,
@@ -767,7 +782,12 @@ __global__ __launch_bounds__(256) void k_mask_pack_holdout(
         const int64_t t = 16 * tt + (l >> 4) + 4 * w;
         const bool real = i < n1l && j < n2 && t < n3;
         const int64_t o = real ? (t * n2 + j) * ld + i : 0;
-        const bool on = !real || !obs || obs[o] != 0;
+        const int64_t e = (blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1);
+        bool on;
+        if constexpr (NANM)
+            on = !real || !is_nan_bits(D[e]);
+        else
+            on = !real || !obs || obs[o] != 0;
         const bool ho = real && on && hold[o] != 0;
         const unsigned long long fw = __ballot(on && !ho), hw = __ballot(ho);
         fitn += __builtin_popcountll(__ballot(real && on && !ho));
@@ -776,7 +796,7 @@ __global__ __launch_bounds__(256) void k_mask_pack_holdout(
             M[blk * MK_WORDS_HO + w] = fw;
             M[blk * MK_WORDS_HO + 4 + w] = hw;
         }
-        if (!on) D[(blk << 8) + ((w >> 1) << 7) + (l << 1) + (w & 1)] = 0.0;
+        if (!on) D[e] = 0.0;
     }
     if (l == 0 && fitn) atomicAdd(count, (unsigned long long)fitn);
     if (l == 0 && hon) atomicAdd(count + 1, (unsigned long long)hon);
@@ -786,8 +806,13 @@ void launch_mask_pack_holdout(const Geom& g, const uint8_t* obs, const uint8_t* 
                               unsigned long long* M, double* D, unsigned long long* count,
                               hipStream_t st) {
     const int64_t ntiles = g.Ntm / 256;
-    hipLaunchKernelGGL(k_mask_pack_holdout, dim3((unsigned)cdiv(ntiles, 4)), dim3(256), 0, st, obs,
-                       hold, ld, g.n1l, g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
+    const dim3 grid((unsigned)cdiv(ntiles, 4)), block(256);
+    if (obs_is_nan(obs))
+        hipLaunchKernelGGL(k_mask_pack_holdout<true>, grid, block, 0, st, nullptr, hold, ld, g.n1l,
+                           g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
+    else
+        hipLaunchKernelGGL(k_mask_pack_holdout<false>, grid, block, 0, st, obs, hold, ld, g.n1l,
+                           g.n2, g.n3, g.n1p, g.ntt, ntiles, M, D, count);
     TRITD_CHECK_LAUNCH();
 }
 

@@ -205,7 +205,10 @@ void launch_from_tm(const Geom& g, const double* src, double* dst, int64_t ld, h
 // opts.observed: the caller's byte mask (column-major shard like D, fibres ld
 // bytes apart, nonzero = observed) -> mask words M (common.h: MK); the
 // unobserved elements of the tile-major D are zeroed and the observed entries
-// of the shard (pads excluded) added to *count
+// of the shard (pads excluded) added to *count.
+// obs = TRITD_OBSERVED_NAN (here and in the two packers below): no byte mask
+// is read, the observed bit is !isnan of the element of D itself (ld then
+// belongs to hold alone).
 void launch_mask_pack(const Geom& g, const uint8_t* obs, int64_t ld, unsigned long long* M,
                       double* D, unsigned long long* count, hipStream_t st);
 // holdout=: obs (or null: all observed) and hold are byte masks like obs above.
@@ -229,9 +232,10 @@ void launch_soft_threshold(const double* X, int64_t n, double lam, double* Y, hi
 // unchanged), the four words of H & Omega at Hw + MK_WORDS b in the same bit
 // layout, and cnt[b] = the tile's held-out count.  Padding is fit-observed and
 // never held out.  *fit_count += |Omega & ~H| of the shard (pads excluded).
+// D (tile-major) is read only when obs = TRITD_OBSERVED_NAN, and not written.
 void launch_ho_pack_words(const Geom& g, const uint8_t* obs, const uint8_t* hold, int64_t ld,
-                          unsigned long long* M, unsigned long long* Hw, unsigned* cnt,
-                          unsigned long long* fit_count, hipStream_t st);
+                          const double* D, unsigned long long* M, unsigned long long* Hw,
+                          unsigned* cnt, unsigned long long* fit_count, hipStream_t st);
 // hoff[b] = sum of cnt[0..b), b = 0..ntiles (hoff[ntiles] = the held-out
 // count): one workgroup, a fixed order, no atomics
 void launch_ho_scan(const unsigned* cnt, int64_t ntiles, unsigned long long* hoff, hipStream_t st);

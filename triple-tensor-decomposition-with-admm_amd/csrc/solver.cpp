@@ -394,7 +394,8 @@ void Session::set_normD_from_red3() {
 }
 
 // opts.observed -> M_ (and D zeroed where unobserved).  A host mask is staged
-// as a contiguous n1l x n2 x n3 byte array first.
+// as a contiguous n1l x n2 x n3 byte array first; TRITD_OBSERVED_NAN has no
+// array: the packers read the mask off D_ itself.
 // holdout (or null): a second byte mask of the same layout; M_ then holds the
 // fit words Omega & ~H, and Hw_, hoff_, hvals_ the held-out set (k_holdout.hip).
 void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
@@ -419,7 +420,7 @@ void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
                                            hipMemcpyHostToDevice, st_));
             return reinterpret_cast<const uint8_t*>(b.p);
         };
-        if (observed) src = to_device(stage, observed);
+        if (observed && !obs_is_nan(observed)) src = to_device(stage, observed);
         if (holdout) srch = to_device(stageh, holdout);
         ld = g_.n1l;
     }
@@ -434,7 +435,7 @@ void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
         tcnt.alloc_bytes((size_t)ntiles * sizeof(unsigned));
         unsigned long long* Hw = reinterpret_cast<unsigned long long*>(Hw_.p);
         unsigned long long* hoff = reinterpret_cast<unsigned long long*>(hoff_.p);
-        launch_ho_pack_words(g_, src, srch, ld, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
+        launch_ho_pack_words(g_, src, srch, ld, D_.p, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
                              reinterpret_cast<unsigned long long*>(cnt.p), st_);
         launch_ho_scan(reinterpret_cast<const unsigned*>(tcnt.p), ntiles, hoff, st_);
         unsigned long long nh = 0;

@@ -16,6 +16,12 @@ function [A, B, C, O, errHist, E] = triple_decomp_ADMM(D, r, opts)
 %   rank-r^2 CP builders for the Qi-model design matrices of
 %   origin_triple_tensor/buildF.m, buildG.m, buildH.m (3-index triple
 %   product; reconstruct with triple_product(A, B, C, 'qi')).  Double D only.
+%
+%   opts.nanmissing = 1 (optional; this build's own field): a NaN in D marks a
+%   missing entry, as ~isnan(D) would in a masked call.  The fit uses the
+%   other entries only, O and E are exactly 0 at the missing ones and errHist
+%   counts the observed ones.  The mask is derived on the GPU; opts goes to
+%   tritd_mex unchanged.  Double D only (a single D is refused).
 [n1, n2, n3] = size(D);
 A0 = randn(n1, r, r);
 B0 = randn(r, n2, r);

@@ -2,7 +2,8 @@ function [A, B, C, O, errHist, E] = triple_decomp_ADMM_outlier(D, r, varargin)
 %TRIPLE_DECOMP_ADMM_OUTLIER  Name called by video_triple_comparison.m:54.
 %   triple_decomp_ADMM_outlier(D, r, opts): in the reference this name exists
 %   only as an internal function name (origin_triple_tensor/triple_decomp_ADMM.m:1)
-%   and does not resolve; here it is the same GPU solver as triple_decomp_ADMM.
+%   and does not resolve; here it is the same GPU solver as triple_decomp_ADMM
+%   (opts.nanmissing included: opts is passed through).
 %
 %   triple_decomp_ADMM_outlier(X, r, rho, lambda, gamma_A, epsilon, p, theta,
 %   maxIter, tol) is the signature of fast_robust_triple_tensor/test.m:1, the

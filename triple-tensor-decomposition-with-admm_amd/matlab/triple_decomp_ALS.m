@@ -10,6 +10,10 @@ function [A, B, C, errHist] = triple_decomp_ALS(X, r, opts)
 %   The initial factors are drawn here with randn in the reference's order
 %   (A, then B, then C).  X is processed in double.  tritd_devices(idx)
 %   shards X over several GPUs.
+%
+%   opts.nanmissing = 1 (optional; this build's own field): a NaN in X marks a
+%   missing entry; the fit and errHist use the other entries only (opts goes
+%   to tritd_mex unchanged, the mask is derived on the GPU).
 [n1, n2, n3] = size(X);
 A0 = randn(n1, r, r);
 B0 = randn(r, n2, r);

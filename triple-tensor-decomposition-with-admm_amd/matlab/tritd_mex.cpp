@@ -6,6 +6,10 @@
 //                         rules for a single D)
 //   [A,B,C,errHist] = tritd_mex('als', X, r, opts, A0, B0, C0)
 //                         triple_decomp_ALS (double X) -> tritd_als_f64
+//                         opts.nanmissing (optional scalar, this build's own field):
+//                         nonzero = a NaN in D / X marks a missing entry; 'admm' and
+//                         'als' then fit the others only (tritd_admm_masked_f64 /
+//                         tritd_als_masked_f64 with TRITD_OBSERVED_NAN; double only)
 //   tritd_mex('devices', idx)  HIP device ordinals (0-based) the next solves
 //                         shard D over (tritd_set_devices; [] clears)
 //   X  = tritd_mex('triple_product', A, B, C[, 'qi'])
@@ -84,6 +88,13 @@ bool read_opts(const mxArray* s, tritd_opts* o, std::string* err) {
     return true;
 }
 
+// opts.nanmissing: optional, read after the required fields (their errors and
+// their order are those of the reference)
+bool nan_missing(const mxArray* s) {
+    const mxArray* v = mxGetField(s, 0, "nanmissing");
+    return v && mxGetScalar(v) != 0.0;
+}
+
 // [n1,n2,n3] = size(X) with MATLAB's trailing-singleton rule; > 3 dims is
 // refused (the reference fails at D - O, triple_decomp_ADMM.m:33)
 bool size3(const mxArray* X, int64_t d[3], std::string* err) {
@@ -142,12 +153,24 @@ void do_admm(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     tritd_opts o;
     if (!read_opts(prhs[3], &o, &err))
         fail(err.rfind("Reference", 0) == 0 ? "MATLAB:nonExistentField" : "tritd:opts", err);
+    const bool nanm = nan_missing(prhs[3]);
     for (int k = 4; k < 7; ++k) need_double(prhs[k], "initial factor");
     const int64_t R = (int64_t)r * r;
     if ((int64_t)mxGetNumberOfElements(prhs[4]) != n[0] * R ||
         (int64_t)mxGetNumberOfElements(prhs[5]) != R * n[1] ||
         (int64_t)mxGetNumberOfElements(prhs[6]) != R * n[2])
         fail("tritd:dims", "A0, B0, C0 must be n1 x r x r, r x n2 x r, r x r x n3");
+    if (single && nanm) {
+        // no mask on the single path: the refusal is the library's own (that of
+        // a masked fp32 session, given before any device is touched)
+        tritd_session* s = nullptr;
+        const tritd_status st = tritd_session_create_masked(
+            &s, 0, mxGetData(D), TRITD_OBSERVED_NAN, n[0], n[0], n[1], n[2], 0, n[0], r, &o,
+            mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]), nullptr, TRITD_SESSION_F32);
+        if (st == TRITD_OK) tritd_session_destroy(s);
+        fail(st == TRITD_ERR_OPTS ? "MATLAB:nonExistentField" : "tritd:solver",
+             st == TRITD_OK ? std::string("opts.nanmissing needs a double D") : status_msg(st));
+    }
 
     mxArray* A = make3(n[0], r, r);
     mxArray* B = make3(r, n[1], r);
@@ -167,10 +190,12 @@ void do_admm(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                 mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]), mxGetPr(A),
                                 mxGetPr(B), mxGetPr(C), static_cast<float*>(data(O)),
                                 static_cast<float*>(data(E)), ehp, &k, -1)
-               : tritd_admm_f64(mxGetPr(D), n[0], n[1], n[2], r, &o, mxGetPr(prhs[4]),
-                                mxGetPr(prhs[5]), mxGetPr(prhs[6]), mxGetPr(A), mxGetPr(B),
-                                mxGetPr(C), static_cast<double*>(data(O)),
-                                static_cast<double*>(data(E)), ehp, &k, -1);
+               // (observed = NULL is tritd_admm_f64)
+               : tritd_admm_masked_f64(mxGetPr(D), nanm ? TRITD_OBSERVED_NAN : nullptr, n[0], n[1],
+                                       n[2], r, &o, mxGetPr(prhs[4]), mxGetPr(prhs[5]),
+                                       mxGetPr(prhs[6]), mxGetPr(A), mxGetPr(B), mxGetPr(C),
+                                       static_cast<double*>(data(O)),
+                                       static_cast<double*>(data(E)), ehp, &k, -1);
     if (st != TRITD_OK) {
         for (mxArray* x : {A, B, C, O, E, eh})
             if (x) mxDestroyArray(x);
@@ -219,6 +244,7 @@ void do_als(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     const int32_t r = (int32_t)mxGetScalar(prhs[2]);
     tritd_opts o;
     if (!read_als_opts(prhs[3], &o, &err)) fail("MATLAB:nonExistentField", err);
+    const bool nanm = nan_missing(prhs[3]);
     for (int k = 4; k < 7; ++k) need_double(prhs[k], "initial factor");
     const int64_t R = (int64_t)r * r;
     if ((int64_t)mxGetNumberOfElements(prhs[4]) != n[0] * R ||
@@ -231,10 +257,11 @@ void do_als(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxArray* eh = mxCreateDoubleMatrix(o.maxIter > 0 ? o.maxIter : 0, 1, mxREAL);
     int32_t k = 0;
     tritd_set_print_callback(print_line, nullptr);
-    const tritd_status st = tritd_als_f64(mxGetPr(prhs[1]), n[0], n[1], n[2], r, &o,
-                                          mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]),
-                                          mxGetPr(A), mxGetPr(B), mxGetPr(C),
-                                          o.maxIter > 0 ? mxGetPr(eh) : nullptr, &k, -1);
+    // (observed = NULL is tritd_als_f64)
+    const tritd_status st = tritd_als_masked_f64(
+        mxGetPr(prhs[1]), nanm ? TRITD_OBSERVED_NAN : nullptr, n[0], n[1], n[2], r, &o,
+        mxGetPr(prhs[4]), mxGetPr(prhs[5]), mxGetPr(prhs[6]), mxGetPr(A), mxGetPr(B), mxGetPr(C),
+        o.maxIter > 0 ? mxGetPr(eh) : nullptr, &k, -1);
     if (st != TRITD_OK) {
         for (mxArray* x : {A, B, C, eh}) mxDestroyArray(x);
         fail(st == TRITD_ERR_OPTS ? "MATLAB:nonExistentField" : "tritd:solver", status_msg(st));

@@ -88,14 +88,54 @@ def _size3(X):
     return int(s[0]), int(s[1]), int(s[2])
 
 
+class _ObservedNaN:
+    """observed="nan": Omega = ~isnan(D), derived on the device
+    (TRITD_OBSERVED_NAN of tritd.h: the constant 1 as a pointer, no array)."""
+
+    def __repr__(self):
+        return "observed='nan'"
+
+
+_NAN = _ObservedNaN()
+
+
 def _ptr(a):
+    if a is _NAN:
+        return C.c_void_p(1)
     return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _check_observed(observed):
+    """A string ``observed`` must be exactly "nan" (NaN in the data marks a
+    missing entry); any other string is a ValueError."""
+    if isinstance(observed, str) and observed != "nan":
+        raise ValueError(f'observed must be a logical array or the string "nan", got {observed!r}')
+
+
+def _device_mask(observed):
+    """``observed`` beside a device-resident tensor: a device address, "nan" or None"""
+    if isinstance(observed, str):
+        _check_observed(observed)
+        return _ptr(_NAN)
+    return C.c_void_p(int(observed)) if observed is not None else None
+
+
+def _holdout_count(hold, obs, D):
+    """|H & Omega| on the host; with observed="nan" from the held entries only"""
+    if obs is _NAN:
+        return int(np.count_nonzero(~np.isnan(D[hold.view(np.bool_)])))
+    return int(np.count_nonzero(hold if obs is None else hold & obs))
 
 
 def _observed_bytes(observed, shape, what="D", name="observed"):
     """opts.observed -> a column-major uint8 array of D's shape (nonzero =
     observed); a shape that differs from D's raises like a MATLAB logical
-    index of the wrong size."""
+    index of the wrong size.  observed="nan" -> _NAN (no array is made)."""
+    if isinstance(observed, str):
+        if name != "observed":
+            raise ValueError(f"{name} must be a logical array of the shape of {what}")
+        _check_observed(observed)
+        return _NAN
     m = np.asarray(observed)
     if tuple(m.shape) != tuple(shape):
         raise ValueError(f"{name} must have the shape of {what} {tuple(shape)}, got {tuple(m.shape)}")
@@ -133,6 +173,12 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     errHist counts observed entries only.  float64 D; for mode-1 shards set
     the device set (``set_devices``), not ``virtual_shards``.
 
+    ``observed="nan"`` (exactly that string) takes the mask from the data:
+    Omega = ~isnan(D), derived on the device (TRITD_OBSERVED_NAN), with no host
+    pass over D, no mask array and no upload.  Any NaN counts as missing, Inf
+    is data; every output is bit for bit that of ``observed=~np.isnan(D)``.
+    The other solvers and the session classes take it the same way.
+
     ``holdout`` (a logical array of D's shape; tritd_admm_holdout_f64) withholds
     the entries of ``holdout & observed`` from the fit, which is exactly the
     masked one with ``observed & ~holdout``, and scores them after every
@@ -153,6 +199,7 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     path).  A float32 D runs the single-class path (MATLAB semantics of a
     `single` D: O, E float32; A, B, C, errHist float64), r <= 16."""
     o = make_opts(opts)
+    _check_observed(observed)
     if np.asarray(D).dtype == np.float32:
         if observed is not None or holdout is not None:
             raise TritdError(_lib.TRITD_ERR_UNSUPPORTED,
@@ -194,7 +241,7 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
                                                _ptr(Bb), _ptr(Cb), _ptr(valHist), _ptr(valHist1),
                                                C.byref(best), C.byref(why), int(device)),
                     "triple_decomp_ADMM")
-        count = int(np.count_nonzero(hold if obs is None else hold & obs))
+        count = _holdout_count(hold, obs, D)
         out = [A, B, Cf, O, errHist[: k.value].copy()]
         if return_E:
             out.append(E)
@@ -273,6 +320,8 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
     observed entries only, and the factor updates take where(observed, X, T)
     for X.  With every entry observed the result is the unmasked one, bit for
     bit.  For mode-1 shards set the device set (``set_devices``).
+    ``observed="nan"``: Omega = ~isnan(X), derived on the device (see
+    ``triple_decomp_ADMM``).
 
     ``holdout`` (a logical array of X's shape; tritd_ncvx_holdout_f64) withholds
     the entries of ``holdout & observed`` from the fit, which is exactly the
@@ -316,7 +365,7 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
                                                _ptr(Ab), _ptr(Bb), _ptr(Cb), _ptr(valHist),
                                                _ptr(valHist1), C.byref(best), C.byref(why),
                                                int(device)), "triple_decomp_ADMM_outlier")
-        count = int(np.count_nonzero(hold if obs is None else hold & obs))
+        count = _holdout_count(hold, obs, X)
         out = [A, B, Cf, O, errHist[: k.value].copy()]
         if return_iters:
             out.append(k.value)
@@ -369,6 +418,8 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
     entries are never used (NaN allowed), the updates see the current model
     there, and errHist counts observed entries only.  For mode-1 shards set
     the device set (``set_devices``), not ``virtual_shards``.
+    ``observed="nan"``: Omega = ~isnan(X), derived on the device (see
+    ``triple_decomp_ADMM``).
 
     ``holdout`` (a logical array of X's shape; tritd_als_holdout_f64) withholds
     the entries of ``holdout & observed`` from the fit, which is exactly the
@@ -419,7 +470,7 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
                                               C.byref(k), _ptr(Ab), _ptr(Bb), _ptr(Cb),
                                               _ptr(valHist), C.byref(best), C.byref(why),
                                               int(device)), "triple_decomp_ALS")
-        count = int(np.count_nonzero(hold if obs is None else hold & obs))
+        count = _holdout_count(hold, obs, X)
         out = [A, B, Cf, errHist[: k.value].copy()]
         if return_iters:
             out.append(k.value)
@@ -564,7 +615,8 @@ class Session:
 
     ``observed`` is the mask of the shard (tritd_session_create_masked): with
     a host D a logical array of D's shape, with ``d_device_ptr`` a device
-    pointer to bytes laid out like D (fibres ldD bytes apart).  float64 only.
+    pointer to bytes laid out like D (fibres ldD bytes apart); in either case
+    ``"nan"`` for Omega = ~isnan(D), derived on the device.  float64 only.
 
     ``holdout`` (given like ``observed``), ``patience`` and ``val_norm`` make it
     a holdout session (tritd_session_create_holdout; see
@@ -595,7 +647,7 @@ class Session:
             dptr = C.c_void_p(int(d_device_ptr))
             flags |= _lib.SESSION_D_ON_DEVICE
             ldD = ldD if ldD is not None else (i1 - i0)
-            optr = C.c_void_p(int(observed)) if observed is not None else None
+            optr = _device_mask(observed)
             hptr = C.c_void_p(int(holdout)) if holdout is not None else None
         else:
             D = np.asfortranarray(D, dtype=np.float32 if self.f32 else np.float64)
@@ -761,7 +813,8 @@ class AlsSession:
 
     ``observed`` is the mask of the shard (tritd_als_session_create_masked):
     with a host X a logical array of X's shape, with ``x_device_ptr`` a device
-    pointer to bytes laid out like X (fibres ldX bytes apart).
+    pointer to bytes laid out like X (fibres ldX bytes apart); in either case
+    ``"nan"`` for Omega = ~isnan(X), derived on the device.
 
     ``ncvx=dict(rho=, lam=, gamma_A=, epsilon=, p=, theta=)`` turns the session,
     masked or not, into the nonconvex solver of test.m:1-73
@@ -791,7 +844,7 @@ class AlsSession:
             xptr = C.c_void_p(int(x_device_ptr))
             flags |= _lib.SESSION_D_ON_DEVICE
             ldX = ldX if ldX is not None else (i1 - i0)
-            optr = C.c_void_p(int(observed)) if observed is not None else None
+            optr = _device_mask(observed)
             hptr = C.c_void_p(int(holdout)) if holdout is not None else None
         else:
             X = _fortran(X)
@@ -940,7 +993,7 @@ class NcvxSession(AlsSession):
             xptr = C.c_void_p(int(x_device_ptr))
             flags |= _lib.SESSION_D_ON_DEVICE
             ldX = ldX if ldX is not None else (i1 - i0)
-            optr = C.c_void_p(int(observed)) if observed is not None else None
+            optr = _device_mask(observed)
             hptr = C.c_void_p(int(holdout))
         else:
             X = _fortran(X)

@@ -61,10 +61,22 @@ def missing_mask(shape, ratio, rng):
     return mask.reshape(shape, order="F")
 
 
-def _observe(X, mask):
+def _observe(X, mask, fill=0.0):
     Y = np.array(X, dtype=np.float64, order="F", copy=True)
-    Y[mask] = 0.0
+    Y[mask] = fill
     return Y
+
+
+def _mask_args(use_mask, mask):
+    """use_mask -> (the fill of the missing entries, the solver's `observed`):
+    False: zeros and no mask (the reference); True: zeros and `~mask`; "nan":
+    NaN at the missing entries and observed="nan" (the mask is then derived
+    from the data on the device)."""
+    if isinstance(use_mask, str):
+        if use_mask != "nan":
+            raise ValueError('use_mask must be False, True or "nan", got %r' % (use_mask,))
+        return np.nan, "nan"
+    return 0.0, (~mask if use_mask else None)
 
 
 def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0=None, C0=None,
@@ -74,16 +86,18 @@ def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0
     entries with `evaluate(X_hat, X, true(size(X)))`, print as at :64.
     `use_mask` (not in the reference, which lets the solver explain the zeros
     as outliers) tells the solver which entries are missing
-    (`observed = ~mask`): it then fits the observed ones only."""
+    (`observed = ~mask`): it then fits the observed ones only.
+    `use_mask="nan"` writes NaN at the missing entries instead of zeros and
+    passes `observed="nan"`: the same fit, with no mask array made or uploaded."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     rng = np.random.default_rng(seed)
     mask = missing_mask(X.shape, missing_ratio, rng)
     printer("\n===== Dataset: %s Missing Radio %.3f=====" % (name, missing_ratio))
-    Y = _observe(X, mask)
+    fill, observed = _mask_args(use_mask, mask)
+    Y = _observe(X, mask, fill)
     o = dict(TRAFFIC_OPTS if opts is None else opts)
     t0 = time.perf_counter()
-    A, B, C, O, errHist = api.triple_decomp_ADMM(Y, r, o, A0, B0, C0,
-                                                 observed=~mask if use_mask else None)
+    A, B, C, O, errHist = api.triple_decomp_ADMM(Y, r, o, A0, B0, C0, observed=observed)
     timer = time.perf_counter() - t0
     X_hat = api.triple_product(A, B, C)
     rmse, nrmse = api.evaluate(X_hat, X)
@@ -101,12 +115,14 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     :74-75.  With `save_dir` the observed tensor is saved as `<name>_raw.mat`
     (variable Y, :32, every ratio) and, when missing_ratio == plot_rate == 0
     (:58), the errHist / X_hat / O .mat files of :59-61.  `use_mask` passes
-    `observed = ~mask` to the solver (see traffic_triple)."""
+    `observed = ~mask` to the solver, `use_mask="nan"` NaN-marked data and
+    `observed="nan"` (see traffic_triple)."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     rng = np.random.default_rng(seed)
     mask = missing_mask(X.shape, missing_ratio, rng)
     printer("\n===== Dataset: %s Missing Radio %.3f=====" % (name, missing_ratio))
-    Y = _observe(X, mask)
+    fill, observed = _mask_args(use_mask, mask)
+    Y = _observe(X, mask, fill)
     if save_dir is not None:  # save(sprintf("%s_raw.mat", name), 'Y')  (:32)
         from scipy.io import savemat
         savemat(os.path.join(save_dir, "%s_raw.mat" % name), {"Y": Y})
@@ -115,7 +131,7 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     o = dict(VIDEO_OPTS if opts is None else opts)
     t0 = time.perf_counter()
     A, B, C, O, errHist = api.triple_decomp_ADMM_outlier(Y, r, o, A0, B0, C0,
-                                                         **(dict(observed=~mask) if use_mask else {}))
+                                                         **(dict(observed=observed) if use_mask else {}))
     timer = time.perf_counter() - t0
     X_hat = api.triple_product(A, B, C)
     if save_dir is not None and missing_ratio == 0:
@@ -154,7 +170,8 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
     solved by `triple_decomp_ALS(observed=, holdout=H, patience=)`, and the
     rank whose minimum valHist is smallest wins (the first on a tie).
 
-    `observed=None` means every entry.  `factors(r)` returns (A0, B0, C0) for a
+    `observed=None` means every entry, `observed="nan"` the entries of X that
+    are not NaN (the solver then takes its mask from X too).  `factors(r)` returns (A0, B0, C0) for a
     rank (default: drawn by the solver).  Returns dict(rank=, holdout=H,
     results={r: dict(min_val=, best_iter=, stop_reason=, k=, A=, B=, C=,
     valHist=, errHist=)}) with A, B, C the best iterate's factors.
@@ -175,7 +192,12 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
     `gamma_A` of `opts`).  It is otherwise like "admm": the result also has
     `lam=` and `gamma_A=`, and `results` is keyed by (r, lambda, gamma_A)."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
-    obs = np.ones(X.shape, dtype=bool) if observed is None else np.asarray(observed) != 0
+    if isinstance(observed, str):  # "nan": H needs the positions, the solver derives its own mask
+        api._check_observed(observed)
+        obs, obs_arg = ~np.isnan(X), observed
+    else:
+        obs = np.ones(X.shape, dtype=bool) if observed is None else np.asarray(observed) != 0
+        obs_arg = obs
     H = holdout_mask(obs, holdout_ratio, np.random.default_rng(seed))
     if isinstance(solver, str) and solver not in ("als", "admm", "ncvx"):
         raise ValueError("solver must be 'als', 'admm', 'ncvx' or a callable")
@@ -198,7 +220,7 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
                     _, _, _, _, errHist, k, v = api.triple_decomp_ncvx(
                         X, r, prm["rho"], lam, gam, prm["epsilon"], prm["p"], prm["theta"],
                         prm["maxIter"], prm["tol"], A0, B0, C0, device=device, return_iters=True,
-                        observed=obs, holdout=H, patience=patience, val_norm=val_norm)
+                        observed=obs_arg, holdout=H, patience=patience, val_norm=val_norm)
                     key = (r, lam, gam)
                     results[key] = dict(
                         min_val=float(v[hist][v["best_iter"] - 1]), best_iter=v["best_iter"],
@@ -220,8 +242,8 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
                 o = dict(opts)
                 o["lambda"] = lam
                 _, _, _, _, errHist, k, v = api.triple_decomp_ADMM(
-                    X, r, o, A0, B0, C0, device=device, return_iters=True, observed=obs, holdout=H,
-                    patience=patience, val_norm=val_norm)
+                    X, r, o, A0, B0, C0, device=device, return_iters=True, observed=obs_arg,
+                    holdout=H, patience=patience, val_norm=val_norm)
                 results[(r, lam)] = dict(
                     min_val=float(v[hist][v["best_iter"] - 1]), best_iter=v["best_iter"],
                     stop_reason=v["stop_reason"], k=k, A=v["A_best"], B=v["B_best"], C=v["C_best"],
@@ -235,7 +257,7 @@ def select_rank(X, observed, ranks, holdout_ratio=0.15, opts=None, seed=0, patie
     for r in ranks:
         A0, B0, C0 = factors(r) if factors is not None else (None, None, None)
         _, _, _, errHist, k, v = solve(X, r, o, A0, B0, C0, device=device, return_iters=True,
-                                       observed=obs, holdout=H, patience=patience)
+                                       observed=obs_arg, holdout=H, patience=patience)
         results[r] = dict(min_val=float(v["valHist"][v["best_iter"] - 1]), best_iter=v["best_iter"],
                           stop_reason=v["stop_reason"], k=k, A=v["A_best"], B=v["B_best"],
                           C=v["C_best"], valHist=v["valHist"], errHist=errHist)
