@@ -49,7 +49,8 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 
 // out (row stride ldo, RP x RP, zero outside R x R) = pinv(A), A symmetric
 // RP x RP with row stride ld and a zero pad beyond R; A and V (row stride ld)
-// are overwritten.  rot: 2*RP doubles, pq: RP ints, red: NT/64 + RP doubles
+// are overwritten.  rot: RP doubles (c, s of the RP/2 pairs of a round), pq: RP
+// ints, red: NT/64 + RP doubles
 // (all LDS).  Every thread of the NT-thread workgroup calls it.
 template <int RP, int NT>
 __device__ void jacobi_pinv(double* A, double* V, int ld, int R, double* out, int ldo,
