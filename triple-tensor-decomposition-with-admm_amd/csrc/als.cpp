@@ -24,18 +24,17 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
                        int64_t n3, int64_t i0, int64_t i1, int r, int maxIter, double tol,
                        const double* A0, const double* B0, const double* C0, tritd_comm* comm,
                        uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                       const uint8_t* observed, const uint8_t* holdout, int patience,
-                       const NcvxParams* ncvx, int val_norm)
-    : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm),
-      patience_(patience), val_norm_(val_norm) {
-    if (holdout && patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-    if (ncvx && !holdout)
+                       const uint8_t* observed, const HoldoutSpec& ho, const NcvxParams* ncvx)
+    : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm) {
+    if (ho.mask && ho.patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+    if (ncvx && !ho.mask)
         throw Error(TRITD_ERR_ARG, "a nonconvex session without a holdout is made by enable_ncvx");
-    if (ncvx && val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+    if (ncvx && ho.val_norm != 1 && ho.val_norm != 2)
+        throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
     if (ncvx && !(ncvx->rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
     try {  // (a constructor that throws runs no destructor: an all-false mask is refused here)
         init(X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, flags, shared_stream, defer_norm, observed,
-             holdout, ncvx);
+             ho, ncvx);
     } catch (...) {
         release();
         throw;
@@ -45,7 +44,8 @@ AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int
 void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
                       int64_t i1, int r, const double* A0, const double* B0, const double* C0,
                       uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                      const uint8_t* observed, const uint8_t* holdout, const NcvxParams* ncvx) {
+                      const uint8_t* observed, const HoldoutSpec& ho, const NcvxParams* ncvx) {
+    const uint8_t* holdout = ho.mask;
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
     hoscore_ = holdout && ncvx;
@@ -92,20 +92,8 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     TRITD_HIP(hipMemsetAsync(ctrl_, 0, 4 * sizeof(int), st_));
     if (holdout) {
         holdout_ = true;
-        valHist_.alloc(errHist_.n);
-        hbest_.alloc(1);
-        Abest_.alloc(Ah_.n);
-        Bbest_.alloc(Bh_.n);
-        Cbest_.alloc(Ch_.n);
-        for (DBuf* b : {&valHist_, &hbest_})
-            TRITD_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), st_));
-        if (hoscore_) {
-            valHist1_.alloc(errHist_.n);
-            hopart_.alloc(2 * (size_t)ho_score_grid(g_));
-            TRITD_HIP(hipMemsetAsync(valHist1_.p, 0, valHist1_.n * sizeof(double), st_));
-        }
-        TRITD_HIP(hipMalloc(&hctrl_, 4 * sizeof(int)));
-        TRITD_HIP(hipMemsetAsync(hctrl_, 0, 4 * sizeof(int), st_));
+        val_.alloc(errHist_.n, /*l1=*/hoscore_, Ah_.n, Bh_.n, Ch_.n, ho, st_);
+        if (hoscore_) hset_.alloc(g_);
     }
 
     // X -> tile-major, and its TX copy for the mode-3 contraction (one-off)
@@ -143,11 +131,7 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     TRITD_HIP(hipMemcpy(Bh_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
     TRITD_HIP(hipMemcpy(Ch_.p, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
     TRITD_HIP(hipMemcpy(ChT_.p, ChT.data(), ChT.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (holdout_) {  // best_iter = 0 until the first iteration: A0, B0, C0
-        TRITD_HIP(hipMemcpy(Abest_.p, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
-        TRITD_HIP(hipMemcpy(Bbest_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
-        TRITD_HIP(hipMemcpy(Cbest_.p, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if (holdout_) val_.seed(Ah_.p, Bh_.p, Ch_.p);
 
     // Xnorm = norm(X(:))  (:6)
     const int nb = sumsq_blocks(g_);
@@ -157,7 +141,7 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
         // red0 = {Xnorm^2, |Omega & ~H|, ||H o Omega o X||^2, |H & Omega|, sum |H o Omega o X|}
         launch_sumsq_padded(g_, X_.p, sqpart_.p, nb, st_);
         launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
-        const double c[4] = {(double)obs_count_, ho_sums_[0], (double)ho_count_, ho_sums_[1]};
+        const double c[4] = {(double)obs_count_, hset_.sums[0], hset_.sums[1], hset_.sums[2]};
         TRITD_HIP(hipMemcpyAsync(red0_.p + 1, c, sizeof c, hipMemcpyHostToDevice, st_));
         TRITD_HIP(hipStreamSynchronize(st_));
     } else if (holdout_) {
@@ -167,7 +151,7 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
         launch_sumsq_holdout(g_, X_.p, reinterpret_cast<const unsigned long long*>(M_.p), sqpart_.p,
                              nb, st_);
         launch_reduce_pairs(sqpart_.p, nb, red0_.p, nullptr, st_);
-        const double c[2] = {(double)obs_count_, (double)ho_count_};
+        const double c[2] = {(double)obs_count_, (double)val_.count};
         TRITD_HIP(hipMemcpyAsync(red0_.p + 2, red0_.p + 1, sizeof(double), hipMemcpyDeviceToDevice,
                                  st_));
         TRITD_HIP(hipMemcpyAsync(red0_.p + 1, &c[0], sizeof(double), hipMemcpyHostToDevice, st_));
@@ -200,8 +184,6 @@ void AlsSession::release() {
     ev_.clear();
     if (ctrl_) hip_quiet(hipFree(ctrl_));
     ctrl_ = nullptr;
-    if (hctrl_) hip_quiet(hipFree(hctrl_));
-    hctrl_ = nullptr;
     if (own_stream_ && st_) hip_quiet(hipStreamDestroy(st_));
     st_ = nullptr;
 }
@@ -213,96 +195,41 @@ void AlsSession::set_norm_from_red0() {
     TRITD_HIP(hipMemcpyAsync(ss, red0_.p, norm_count() * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     Xnorm_ = std::sqrt(ss[0]);
-    if ((masked_ || holdout_) && ss[1] == 0.0)
-        throw Error(TRITD_ERR_ARG, holdout_ ? "no observed entry is left to fit beside the holdout"
-                                            : "observed has no true entry: nothing to fit");
-    if (holdout_) {
-        Hnorm_ = std::sqrt(ss[2]);
-        Hsum1_ = ss[4];
-        if (ss[3] == 0.0) throw Error(TRITD_ERR_ARG, "holdout has no observed entry: nothing to score");
-        if (ss[2] == 0.0) throw Error(TRITD_ERR_ARG, "the held-out entries of X are all zero");
-    }
+    check_creation_sums(ss, masked_, holdout_, "X");
+    val_.Hnorm = std::sqrt(ss[2]);  // (zero without a holdout)
+    val_.Hsum1 = ss[4];
 }
 
-// observed -> M_ (and X zeroed where unobserved), as Session::pack_mask.  A
-// host mask is staged as a contiguous n1l x n2 x n3 byte array first.
+// observed -> M_ (and X zeroed where unobserved), as Session::pack_mask.
 // holdout (or null): a second byte mask of the same layout; the words are then
-// those of launch_mask_pack_holdout and X keeps its held-out values.
+// those of launch_mask_pack_holdout and X keeps its held-out values.  The
+// nonconvex holdout form packs like the ADMM: fit words
+// Omega & ~H into M_, the held-out set into hset_, X_ zeroed outside the fit words.
 void AlsSession::pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
                            const uint8_t* holdout) {
     masked_ = true;
     M_.alloc_bytes((size_t)(g_.Ntm / 256) * (holdout && !hoscore_ ? MK_WORDS_HO : MK_WORDS) *
                    sizeof(unsigned long long));
-    DBuf cnt, stage, stageh;
-    cnt.alloc(2);
-    TRITD_HIP(hipMemsetAsync(cnt.p, 0, 2 * sizeof(double), st_));
-    const uint8_t* src = observed;
-    const uint8_t* srch = holdout;
-    int64_t ld = ldX;
-    if (!on_device) {
-        const size_t rows = (size_t)(g_.n2 * g_.n3);
-        auto to_device = [&](DBuf& b, const uint8_t* m) {
-            b.alloc_bytes((size_t)g_.n1l * rows);
-            if (ldX == g_.n1l)
-                TRITD_HIP(hipMemcpyAsync(b.p, m, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
-            else
-                TRITD_HIP(hipMemcpy2DAsync(b.p, (size_t)g_.n1l, m, (size_t)ldX, (size_t)g_.n1l, rows,
-                                           hipMemcpyHostToDevice, st_));
-            return reinterpret_cast<const uint8_t*>(b.p);
-        };
-        if (observed && !obs_is_nan(observed)) src = to_device(stage, observed);
-        if (holdout) srch = to_device(stageh, holdout);
-        ld = g_.n1l;
-    }
+    const StagedMasks m(g_, observed, holdout, ldX, on_device, st_);
+    unsigned long long* M = reinterpret_cast<unsigned long long*>(M_.p);
     if (hoscore_) {
-        pack_mask_score(src, srch, ld);
+        obs_count_ = hset_.pack(g_, m.obs, m.hold, m.ld, X_.p, M, st_);
+        val_.count = hset_.count;
         return;
     }
+    DBuf cnt;
+    cnt.alloc(2);
+    TRITD_HIP(hipMemsetAsync(cnt.p, 0, 2 * sizeof(double), st_));
+    unsigned long long* dc = reinterpret_cast<unsigned long long*>(cnt.p);
     if (holdout)
-        launch_mask_pack_holdout(g_, src, srch, ld, reinterpret_cast<unsigned long long*>(M_.p),
-                                 X_.p, reinterpret_cast<unsigned long long*>(cnt.p), st_);
+        launch_mask_pack_holdout(g_, m.obs, m.hold, m.ld, M, X_.p, dc, st_);
     else
-        launch_mask_pack(g_, src, ld, reinterpret_cast<unsigned long long*>(M_.p), X_.p,
-                         reinterpret_cast<unsigned long long*>(cnt.p), st_);
+        launch_mask_pack(g_, m.obs, m.ld, M, X_.p, dc, st_);
     unsigned long long c[2] = {0, 0};
     TRITD_HIP(hipMemcpyAsync(c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     obs_count_ = (int64_t)c[0];
-    ho_count_ = (int64_t)c[1];
-}
-
-// The nonconvex holdout form: fit words Omega & ~H into M_,
-// the held-out set into Hw_, hoff_, hvals_, X_ zeroed outside the fit words;
-// the two sums of the held-out values in a fixed order (as Session::pack_mask).
-void AlsSession::pack_mask_score(const uint8_t* src, const uint8_t* srch, int64_t ld) {
-    const int64_t ntiles = g_.Ntm / 256;
-    DBuf cnt, tcnt, vpart, vsum;
-    cnt.alloc(1);
-    TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
-    Hw_.alloc_bytes((size_t)ntiles * MK_WORDS * sizeof(unsigned long long));
-    hoff_.alloc((size_t)ntiles + 1);
-    tcnt.alloc_bytes((size_t)ntiles * sizeof(unsigned));
-    unsigned long long* M = reinterpret_cast<unsigned long long*>(M_.p);
-    unsigned long long* Hw = reinterpret_cast<unsigned long long*>(Hw_.p);
-    unsigned long long* hoff = reinterpret_cast<unsigned long long*>(hoff_.p);
-    launch_ho_pack_words(g_, src, srch, ld, X_.p, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
-                         reinterpret_cast<unsigned long long*>(cnt.p), st_);
-    launch_ho_scan(reinterpret_cast<const unsigned*>(tcnt.p), ntiles, hoff, st_);
-    unsigned long long nh = 0, c = 0;
-    TRITD_HIP(hipMemcpyAsync(&nh, hoff + ntiles, sizeof nh, hipMemcpyDeviceToHost, st_));
-    TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
-    TRITD_HIP(hipStreamSynchronize(st_));
-    ho_count_ = (int64_t)nh;
-    obs_count_ = (int64_t)c;
-    hvals_.alloc((size_t)nh);
-    launch_ho_pack_vals(g_, M, Hw, hoff, X_.p, hvals_.p, st_);
-    const int nb = ho_sum_blocks(ho_count_);
-    vpart.alloc(2 * (size_t)nb);
-    vsum.alloc(2);
-    launch_ho_valsum(hvals_.p, ho_count_, vpart.p, nb, st_);
-    launch_reduce_pairs(vpart.p, nb, vsum.p, nullptr, st_);
-    TRITD_HIP(hipMemcpyAsync(ho_sums_, vsum.p, sizeof ho_sums_, hipMemcpyDeviceToHost, st_));
-    TRITD_HIP(hipStreamSynchronize(st_));
+    val_.count = (int64_t)c[1];
 }
 
 void AlsSession::allreduce(double* buf, int64_t count) {
@@ -366,12 +293,8 @@ void AlsSession::phaseFit(int k) {
     if (hoscore_) {
         // XT_ holds T_k (:35) at every entry outside the fit mask; the two score
         // sums ride behind the fit sums in the same all-reduce
-        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 5], st_));
-        launch_ho_score(g_, XT_.p, reinterpret_cast<const unsigned long long*>(Hw_.p),
-                        reinterpret_cast<const unsigned long long*>(hoff_.p), hvals_.p, hopart_.p,
-                        ctrl_, st_);
-        if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 6], st_));
-        launch_reduce_pairs(hopart_.p, ho_score_grid(g_), red0_.p + 2, ctrl_, st_);
+        hset_.score(g_, XT_.p, red0_.p + 2, ctrl_, st_, timing_ ? ev_[ev_base_ + 5] : nullptr,
+                    timing_ ? ev_[ev_base_ + 6] : nullptr);
     }
 }
 
@@ -379,10 +302,9 @@ void AlsSession::phaseErr(int k) {
     if (hoscore_) {
         // both scores and the running best; the factors iteration k started
         // with are kept, before the A update, if k is the best so far
-        launch_ncvx_ho_mark(red0_.p + 2, Hnorm_, Hsum1_, k, val_norm_, valHist_.p, valHist1_.p,
-                            ctrl_, hctrl_, hbest_.p, st_);
-        launch_als_snapshot(Ah_.p, Bh_.p, Ch_.p, Abest_.p, Bbest_.p, Cbest_.p, (int64_t)Ah_.n,
-                            (int64_t)Bh_.n, (int64_t)Ch_.n, hctrl_, st_);
+        launch_ncvx_ho_mark(red0_.p + 2, val_.Hnorm, val_.Hsum1, k, val_.val_norm, val_.valHist.p,
+                            val_.valHist1.p, ctrl_, val_.hctrl, val_.hbest.p, st_);
+        val_.snapshot(Ah_.p, Bh_.p, Ch_.p, st_);
         if (timing_) TRITD_HIP(hipEventRecord(ev_[ev_base_ + 7], st_));
         return;
     }
@@ -390,10 +312,9 @@ void AlsSession::phaseErr(int k) {
     if (holdout_) {
         // valHist(k), the running best and both stop tests; then the factors
         // iteration k started with are kept if k is the best so far
-        launch_als_finish_holdout(red0_.p, Xnorm_, Hnorm_, k, tol_, patience_, errHist_.p,
-                                  valHist_.p, ctrl_, hctrl_, hbest_.p, st_);
-        launch_als_snapshot(Ah_.p, Bh_.p, Ch_.p, Abest_.p, Bbest_.p, Cbest_.p, (int64_t)Ah_.n,
-                            (int64_t)Bh_.n, (int64_t)Ch_.n, hctrl_, st_);
+        launch_als_finish_holdout(red0_.p, Xnorm_, val_.Hnorm, k, tol_, val_.patience, errHist_.p,
+                                  val_.valHist.p, ctrl_, val_.hctrl, val_.hbest.p, st_);
+        val_.snapshot(Ah_.p, Bh_.p, Ch_.p, st_);
         return;
     }
     launch_als_finish(red0_.p, Xnorm_, k, tol_, errHist_.p, ctrl_, st_);
@@ -404,7 +325,8 @@ void AlsSession::phaseEnd(int k) {
     // errHist(k) = norm(X(:) - Y_new(:) - O_new(:))/Xnorm (:62); the stop flag
     // set here makes every kernel of k+1 exit (:65-67)
     if (hoscore_) {  // + the patience test and stop_reason
-        launch_ncvx_ho_finish(red0_.p, Xnorm_, k, tol_, patience_, errHist_.p, ctrl_, hctrl_, st_);
+        launch_ncvx_ho_finish(red0_.p, Xnorm_, k, tol_, val_.patience, errHist_.p, ctrl_, val_.hctrl,
+                              st_);
         return;
     }
     launch_als_finish(red0_.p, Xnorm_, k, tol_, errHist_.p, ctrl_, st_);
@@ -506,8 +428,8 @@ void AlsSession::harvest_timing() {
             float sc = 0, tl = 0;
             TRITD_HIP(hipEventElapsedTime(&sc, ev_[b + 5], ev_[b + 6]));
             TRITD_HIP(hipEventElapsedTime(&tl, ev_[b + 1], ev_[b + 7]));
-            acc_score_ += sc;
-            acc_tail_ += tl;
+            val_.acc_score += sc;
+            val_.acc_tail += tl;
         }
         ++acc_n_;
     }
@@ -517,7 +439,7 @@ void AlsSession::harvest_timing() {
 
 void AlsSession::set_timing(bool on) {
     timing_ = on;
-    acc_fit_ = acc_m3_ = acc_it_ = acc_score_ = acc_tail_ = 0;
+    acc_fit_ = acc_m3_ = acc_it_ = val_.acc_score = val_.acc_tail = 0;
     acc_n_ = 0;
 }
 
@@ -543,62 +465,26 @@ void AlsSession::sync(int* done, int* stopped) {
 void AlsSession::get(double* A, double* B, double* C, double* errHist, int* iters) {
     int done = 0, stopped = 0;
     sync(&done, &stopped);
-    if (A) {
-        std::vector<double> h(Ah_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Ah_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_A(g_, h, A);
-    }
-    if (B) {
-        std::vector<double> h(Bh_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Bh_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_B(g_, h, B);
-    }
-    if (C) {
-        std::vector<double> h(Ch_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Ch_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_C(g_, h, C);
-    }
+    download_factor(g_, Ah_.p, Ah_.n, unpack_A, A);
+    download_factor(g_, Bh_.p, Bh_.n, unpack_B, B);
+    download_factor(g_, Ch_.p, Ch_.n, unpack_C, C);
     if (errHist && done > 0)
         TRITD_HIP(hipMemcpy(errHist, errHist_.p, (size_t)done * sizeof(double),
                             hipMemcpyDeviceToHost));
     if (iters) *iters = done;
 }
 
-void AlsSession::get_val(double* valHist, int* best_iter, int* stop_reason, double* valHist1) {
-    int done = 0, stopped = 0;
-    sync(&done, &stopped);
+void AlsSession::get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason) {
+    int done = 0;
+    sync(&done, nullptr);
     if (!holdout_) throw Error(TRITD_ERR_STATE, "get_val: not a holdout session");
-    int h[3];
-    TRITD_HIP(hipMemcpy(h, hctrl_, sizeof h, hipMemcpyDeviceToHost));
-    if (valHist && done > 0)
-        TRITD_HIP(hipMemcpy(valHist, valHist_.p, (size_t)done * sizeof(double),
-                            hipMemcpyDeviceToHost));
-    if (valHist1 && hoscore_ && done > 0)
-        TRITD_HIP(hipMemcpy(valHist1, valHist1_.p, (size_t)done * sizeof(double),
-                            hipMemcpyDeviceToHost));
-    if (best_iter) *best_iter = h[0];
-    if (stop_reason) *stop_reason = h[2];
+    val_.get_val(done, valHist, valHist1, best_iter, stop_reason);
 }
 
 void AlsSession::get_best(double* A, double* B, double* C) {
-    int done = 0, stopped = 0;
-    sync(&done, &stopped);
+    sync(nullptr, nullptr);
     if (!holdout_) throw Error(TRITD_ERR_STATE, "get_best: not a holdout session");
-    if (A) {
-        std::vector<double> h(Abest_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Abest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_A(g_, h, A);
-    }
-    if (B) {
-        std::vector<double> h(Bbest_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Bbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_B(g_, h, B);
-    }
-    if (C) {
-        std::vector<double> h(Cbest_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Cbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_C(g_, h, C);
-    }
+    val_.get_best(g_, A, B, C);
 }
 
 void AlsSession::get_O(double* O, int64_t ldO) {

@@ -25,8 +25,8 @@ class AlsSession {
                int64_t i0, int64_t i1, int r, int maxIter, double tol, const double* A0,
                const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
                hipStream_t shared_stream = nullptr, bool defer_norm = false,
-               const uint8_t* observed = nullptr, const uint8_t* holdout = nullptr,
-               int patience = 0, const NcvxParams* ncvx = nullptr, int val_norm = 2);
+               const uint8_t* observed = nullptr, const HoldoutSpec& ho = {},
+               const NcvxParams* ncvx = nullptr);
     ~AlsSession();
     AlsSession(const AlsSession&) = delete;
     AlsSession& operator=(const AlsSession&) = delete;
@@ -57,14 +57,14 @@ class AlsSession {
         if (masked) *masked = masked_ ? 1 : 0;
         if (observed_count) *observed_count = masked_ ? obs_count_ : g_.n1l * g_.n2 * g_.n3;
     }
-    // holdout (or null; a byte mask like observed): the entries of H & Omega are
+    // ho.mask (or null; a byte mask like observed): the entries of H & Omega are
     // withheld from the fit, which is the masked ALS with observed = Omega & ~H,
     // and scored every iteration in the fit kernel's own pass:
     // valHist(k) = ||H o Omega o (X - Xhat)|| / ||H o Omega o X|| (tritd.h,
     // tritd_als_holdout_f64).  patience > 0 stops the loop at k when
     // k - best_iter >= patience.
     //
-    // holdout with ncvx (the constructor's last two arguments):
+    // holdout with ncvx (the constructor's last argument):
     // the nonconvex solver of test.m with the same contract
     // (tritd_ncvx_holdout_f64).  The fit is the masked nonconvex one on
     // Omega & ~H, untouched; it leaves the model value of every held-out
@@ -77,21 +77,15 @@ class AlsSession {
     // held-out entries of the shard, ||H o Omega o X|| over all shards
     // (sum1: sum |H o Omega o X|, nonconvex holdout sessions only)
     void holdout_info(int64_t* count, double* norm, double* sum1 = nullptr) const {
-        if (count) *count = ho_count_;
-        if (norm) *norm = Hnorm_;
-        if (sum1) *sum1 = Hsum1_;
+        val_.info(count, norm, sum1);
     }
     // valHist(1:k), best_iter, stop_reason (0 none, 1 the test of :20, 2 patience)
     // valHist1: the l1 history of a nonconvex holdout session (else untouched)
-    void get_val(double* valHist, int* best_iter, int* stop_reason, double* valHist1 = nullptr);
+    void get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason);
     // nonconvex holdout sessions, timed iterations: ms in the score kernel, and
     // from the end of the fit to the start of the A update (score, reductions,
     // mark, snapshot)
-    void holdout_ms(double* score, double* tail) const {
-        const double n = acc_n_ ? (double)acc_n_ : 1.0;
-        if (score) *score = acc_score_ / n;
-        if (tail) *tail = acc_tail_ / n;
-    }
+    void holdout_ms(double* score, double* tail) const { val_.holdout_ms(acc_n_, score, tail); }
     // the factors iteration best_iter started with (A0, B0, C0 before any run)
     void get_best(double* A, double* B, double* C);
     // doubles of the creation-time reduction: Xnorm^2, observed count
@@ -144,7 +138,7 @@ class AlsSession {
     std::vector<hipEvent_t> ev_;  // per timed iteration: ev_slots() events
     int ev_slots() const { return hoscore_ ? 8 : 5; }
     size_t ev_base_ = 0;  // first event of the iteration being enqueued
-    double acc_fit_ = 0, acc_m3_ = 0, acc_it_ = 0, acc_score_ = 0, acc_tail_ = 0;
+    double acc_fit_ = 0, acc_m3_ = 0, acc_it_ = 0;
     int acc_n_ = 0;
     void harvest_timing();
     bool ncvx_ = false;
@@ -158,30 +152,21 @@ class AlsSession {
     int64_t obs_count_ = 0;
     void pack_mask(const uint8_t* observed, int64_t ldX, bool on_device,
                    const uint8_t* holdout = nullptr);
-    // holdout=: M_ holds eight words per tile, X_ keeps the held-out values.
-    // Control words of their own: hctrl_[0] best_iter, [1] snapshot request,
-    // [2] stop_reason; hbest_[0] = valHist(best_iter).
+    // holdout=: M_ holds eight words per tile, X_ keeps the held-out values;
+    // val_ is the validation state (holdout.h).
     bool holdout_ = false;
-    int patience_ = 0;
-    int64_t ho_count_ = 0;
-    double Hnorm_ = 0.0;
-    int* hctrl_ = nullptr;
-    DBuf valHist_, hbest_, Abest_, Bbest_, Cbest_;
+    BestIterate val_;
     // nonconvex holdout: M_ holds the four fit words per tile (Omega & ~H) the
     // masked nonconvex fit reads, X_ is zero outside them; the held-out set
-    // lives in Hw_ (four words per tile), hoff_ (tile offsets) and hvals_
-    // (compact values), the layout of k_holdout.hip.  The score sums go to
-    // red0_[2..3] beside the fit sums.
+    // lives in hset_ (holdout.h, the layout of k_holdout.hip).  The score sums
+    // go to red0_[2..3] beside the fit sums.
     bool hoscore_ = false;
-    int val_norm_ = 2;
-    double Hsum1_ = 0.0, ho_sums_[2] = {0.0, 0.0};
-    DBuf Hw_, hoff_, hvals_, hopart_, valHist1_;
-    void pack_mask_score(const uint8_t* src, const uint8_t* srch, int64_t ld);
+    HoldoutSet hset_;
     void start_ncvx(const NcvxParams& p);
     void init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
               int64_t i1, int r, const double* A0, const double* B0, const double* C0,
               uint32_t flags, hipStream_t shared_stream, bool defer_norm, const uint8_t* observed,
-              const uint8_t* holdout, const NcvxParams* ncvx);
+              const HoldoutSpec& ho, const NcvxParams* ncvx);
     void release();  // what the destructor frees beyond the members' own
 };
 

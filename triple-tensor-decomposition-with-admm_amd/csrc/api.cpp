@@ -509,17 +509,23 @@ void run_threaded(DeviceGroup& grp, F&& shard) {
 // ThreadReducer.  Shard 0 runs on the calling thread, so `disp` prints (the
 // MEX's mexPrintf) stay on the host's own thread.  D, O, E are column-major
 // n1 x n2 x n3 host arrays of es-byte elements.
-// The holdout arguments of tritd_admm_holdout_f64 (every output may be null).
-struct AdmmHoldoutArgs {
-    const uint8_t* holdout;
-    int patience, val_norm;
+// The holdout arguments of the one-shot holdout calls (tritd_admm_holdout_f64,
+// tritd_als_holdout_f64, tritd_ncvx_holdout_f64; every output may be null;
+// valHist1 is written by the ADMM and the nonconvex solver).
+struct HoldoutArgs {
+    HoldoutSpec spec;
     double *A_best, *B_best, *C_best, *valHist, *valHist1;
     int32_t *best_iter, *stop_reason;
 };
+// the spec of the shard that starts at row i0 (none without holdout arguments)
+HoldoutSpec ho_rows(const HoldoutArgs* ho, int64_t i0) {
+    return ho ? ho->spec.rows(i0) : HoldoutSpec{};
+}
 
 // A rows of the best iterate are shard-local, B and C replicated; every
 // shard holds the same histories and decisions (the sums are all-reduced).
-void get_admm_holdout(Session& s, int p, const AdmmHoldoutArgs& h) {
+template <class S>
+void get_holdout(S& s, int p, const HoldoutArgs& h) {
     int bi = 0, sr = 0;
     s.get_val(p == 0 ? h.valHist : nullptr, p == 0 ? h.valHist1 : nullptr, &bi, &sr);
     s.get_best(h.A_best, p == 0 ? h.B_best : nullptr, p == 0 ? h.C_best : nullptr);
@@ -531,14 +537,14 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
                       int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
                       const double* A0, const double* B0, const double* C0, double* A, double* B,
                       double* C, void* O, void* E, double* errHist, int32_t* iters,
-                      const uint8_t* observed = nullptr, const AdmmHoldoutArgs* ho = nullptr);
+                      const uint8_t* observed = nullptr, const HoldoutArgs* ho = nullptr);
 
 // observed (or null): the byte mask of tritd_admm_masked_f64, laid out like D
 void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags, int64_t n1,
                int64_t n2, int64_t n3, int32_t r, const tritd_opts& o, const double* A0,
                const double* B0, const double* C0, double* A, double* B, double* C, void* O,
                void* E, double* errHist, int32_t* iters, const uint8_t* observed = nullptr,
-               const AdmmHoldoutArgs* ho = nullptr) {
+               const HoldoutArgs* ho = nullptr) {
     {
         // TRITD_SHOV=0: the phase-serial order of round 1 (one host thread
         // enqueues every shard's phases, three reductions per iteration)
@@ -553,14 +559,13 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
     const int P = grp.size();
     if (P == 1) {
         Session s(devs[0], D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, flags, nullptr,
-                  false, observed, ho ? ho->holdout : nullptr, ho ? ho->patience : 0,
-                  ho ? ho->val_norm : 2);
+                  false, observed, ho_rows(ho, 0));
         OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * es);
         s.run(o.maxIter);
         pf.join();
         int k = 0;
         s.get(A, B, C, O, E, n1, errHist, &k, true);
-        if (ho) get_admm_holdout(s, 0, *ho);
+        if (ho) get_holdout(s, 0, *ho);
         g_last_flags |= s.flags();
         if (iters) *iters = k;
         return;
@@ -568,14 +573,13 @@ void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t 
     run_threaded(grp, [&](int p, tritd_comm* comm) {
         const auto [i0, i1] = grp.rows(p, n1);
         Session s(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3, i0, i1, r, o, A0,
-                  B0, C0, comm, flags, nullptr, false, obs_rows(observed, i0),
-                  ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0, ho ? ho->val_norm : 2);
+                  B0, C0, comm, flags, nullptr, false, obs_rows(observed, i0), ho_rows(ho, i0));
         s.run(o.maxIter);
         int k = 0;
         s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
               O ? static_cast<char*>(O) + i0 * es : nullptr,
               E ? static_cast<char*>(E) + i0 * es : nullptr, n1, p == 0 ? errHist : nullptr, &k);
-        if (ho) get_admm_holdout(s, p, *ho);
+        if (ho) get_holdout(s, p, *ho);
         if (p == 0 && iters) *iters = k;
         return s.flags();
     });
@@ -588,7 +592,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
                       int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
                       const double* A0, const double* B0, const double* C0, double* A, double* B,
                       double* C, void* O, void* E, double* errHist, int32_t* iters,
-                      const uint8_t* observed, const AdmmHoldoutArgs* ho) {
+                      const uint8_t* observed, const HoldoutArgs* ho) {
     DeviceGroup grp(devs, n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<Session>> ss;
@@ -598,8 +602,7 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         ss.emplace_back(new Session(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3,
                                     i0, i1, r, o, A0, B0, C0, nullptr, flags, grp.vst,
                                     /*defer_normD=*/true, obs_rows(observed, i0),
-                                    ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0,
-                                    ho ? ho->val_norm : 2));
+                                    ho_rows(ho, i0)));
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
     grp.reduce(ss, &Session::red3, ss[0]->norm_count());
@@ -625,31 +628,10 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         ss[p]->get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
                    O ? static_cast<char*>(O) + i0 * es : nullptr,
                    E ? static_cast<char*>(E) + i0 * es : nullptr, n1, p == 0 ? errHist : nullptr, &k);
-        if (ho) get_admm_holdout(*ss[p], p, *ho);
+        if (ho) get_holdout(*ss[p], p, *ho);
         g_last_flags |= ss[p]->flags();
     }
     if (iters) *iters = k;
-}
-
-// The holdout arguments of tritd_als_holdout_f64 (every output may be null).
-struct HoldoutArgs {
-    const uint8_t* holdout;
-    int patience;
-    double *A_best, *B_best, *C_best, *valHist;
-    int32_t *best_iter, *stop_reason;
-    // tritd_ncvx_holdout_f64 only (used when the solver is the nonconvex one)
-    double* valHist1 = nullptr;
-    int val_norm = 2;
-};
-
-// A rows of the best iterate are shard-local, B and C replicated; every
-// shard holds the same valHist and decisions (the sums are all-reduced).
-void get_holdout(AlsSession& s, int p, const HoldoutArgs& h) {
-    int bi = 0, sr = 0;
-    s.get_val(p == 0 ? h.valHist : nullptr, &bi, &sr, p == 0 ? h.valHist1 : nullptr);
-    s.get_best(h.A_best, p == 0 ? h.B_best : nullptr, p == 0 ? h.C_best : nullptr);
-    if (p == 0 && h.best_iter) *h.best_iter = bi;
-    if (p == 0 && h.stop_reason) *h.stop_reason = sr;
 }
 
 // triple_decomp_ALS over a device set: the ALS phases (als.cpp) with the
@@ -684,8 +666,7 @@ void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, in
         const auto [i0, i1] = grp.rows(p, n1);
         AlsSession s(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0, B0, C0,
                      grp.size() > 1 ? comm : nullptr, 0, nullptr, false,
-                     obs_rows(observed, i0), ho ? ho->holdout + i0 : nullptr,
-                     ho ? ho->patience : 0, ho ? ncvx : nullptr, ho ? ho->val_norm : 2);
+                     obs_rows(observed, i0), ho_rows(ho, i0), ho ? ncvx : nullptr);
         if (ncvx && !ho) s.enable_ncvx(*ncvx);
         s.run(maxIter);
         int k = 0;
@@ -710,9 +691,8 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         TRITD_HIP(hipSetDevice(devs[p]));
         ss.emplace_back(new AlsSession(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0,
                                        B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true,
-                                       obs_rows(observed, i0),
-                                       ho ? ho->holdout + i0 : nullptr, ho ? ho->patience : 0,
-                                       ho ? ncvx : nullptr, ho ? ho->val_norm : 2));
+                                       obs_rows(observed, i0), ho_rows(ho, i0),
+                                       ho ? ncvx : nullptr));
         if (ncvx && !ho) ss.back()->enable_ncvx(*ncvx);
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
@@ -867,8 +847,8 @@ tritd_status tritd_admm_holdout_f64(const double* D, const uint8_t* observed, co
         need(D, "D"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
         check_holdout(opts, patience, val_norm);
         const tritd_opts o = normalized(opts);
-        const AdmmHoldoutArgs ho{holdout, patience, val_norm, A_best, B_best, C_best, valHist,
-                                 valHist1, best_iter, stop_reason};
+        const HoldoutArgs ho{{holdout, patience, val_norm}, A_best, B_best, C_best, valHist,
+                             valHist1, best_iter, stop_reason};
         if (device < 0 && g_devices.size() > 1) {
             run_group(g_devices, D, sizeof(double), 0, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
                       errHist, iters, observed, &ho);
@@ -876,13 +856,13 @@ tritd_status tritd_admm_holdout_f64(const double* D, const uint8_t* observed, co
         }
         const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
         Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, 0, nullptr, false,
-                  observed, holdout, patience, val_norm);
+                  observed, ho.spec);
         OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * sizeof(double));
         s.run(o.maxIter);
         pf.join();
         int k = 0;
         s.get(A, B, C, O, E, n1, errHist, &k, true);
-        get_admm_holdout(s, 0, ho);
+        get_holdout(s, 0, ho);
         g_last_flags |= s.flags();
         if (iters) *iters = k;
     });
@@ -980,7 +960,8 @@ tritd_status tritd_session_create_holdout(tritd_session** out, int32_t device, c
         check_holdout(opts, patience, val_norm);
         const int dev = pick_device(device);
         auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
-                              comm, flags, nullptr, false, observed, holdout, patience, val_norm);
+                              comm, flags, nullptr, false, observed,
+                              HoldoutSpec{holdout, patience, val_norm});
         *out = reinterpret_cast<tritd_session*>(s);
     });
 }
@@ -1321,8 +1302,8 @@ tritd_status tritd_als_holdout_f64(const double* X, const uint8_t* observed, con
         need(X, "X"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
         if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
         const int maxIter = opts->maxIter < 0 ? 0 : opts->maxIter;
-        const HoldoutArgs ho{holdout, patience, A_best, B_best, C_best, valHist, best_iter,
-                             stop_reason};
+        const HoldoutArgs ho{{holdout, patience, 2}, A_best, B_best, C_best, valHist, nullptr,
+                             best_iter, stop_reason};
         if (device < 0 && g_devices.size() > 1) {
             run_als_group(g_devices, X, n1, n2, n3, r, maxIter, opts->tol, A0, B0, C0, A, B, C,
                           errHist, iters, nullptr, nullptr, observed, &ho);
@@ -1330,7 +1311,7 @@ tritd_status tritd_als_holdout_f64(const double* X, const uint8_t* observed, con
         }
         const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
         AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, maxIter, opts->tol, A0, B0, C0, nullptr, 0,
-                     nullptr, false, observed, holdout, patience);
+                     nullptr, false, observed, ho.spec);
         s.run(maxIter);
         int k = 0;
         s.get(A, B, C, errHist, &k);
@@ -1422,8 +1403,8 @@ tritd_status tritd_ncvx_holdout_f64(const double* X, const uint8_t* observed, co
         if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
         const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
         const int mi = maxIter < 0 ? 0 : maxIter;
-        const HoldoutArgs ho{holdout, patience, A_best, B_best, C_best, valHist, best_iter,
-                             stop_reason, valHist1, val_norm};
+        const HoldoutArgs ho{{holdout, patience, val_norm}, A_best, B_best, C_best, valHist,
+                             valHist1, best_iter, stop_reason};
         if (device < 0 && g_devices.size() > 1) {
             run_als_group(g_devices, X, n1, n2, n3, r, mi, tol, A0, B0, C0, A, B, C, errHist, iters,
                           &np, O, observed, &ho);
@@ -1431,7 +1412,7 @@ tritd_status tritd_ncvx_holdout_f64(const double* X, const uint8_t* observed, co
         }
         const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
         AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, mi, tol, A0, B0, C0, nullptr, 0, nullptr,
-                     false, observed, holdout, patience, &np, val_norm);
+                     false, observed, ho.spec, &np);
         s.run(mi);
         int k = 0;
         s.get(A, B, C, errHist, &k);
@@ -1453,11 +1434,11 @@ tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, c
 
 // the checks and the construction shared by the three session creators
 static void als_session_create(tritd_als_session** out, int32_t device, const double* X,
-                        const uint8_t* observed, const uint8_t* holdout, int32_t patience,
-                        int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0, int64_t i1,
+                        const uint8_t* observed, const HoldoutSpec& ho, int64_t ldX, int64_t n1,
+                        int64_t n2, int64_t n3, int64_t i0, int64_t i1,
                         int32_t r, const tritd_opts* opts, const double* A0, const double* B0,
                         const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet,
-                        const NcvxParams* ncvx = nullptr, int32_t val_norm = 2) {
+                        const NcvxParams* ncvx = nullptr) {
     need(out, "out");
     *out = nullptr;
     check_als_opts(opts);
@@ -1470,7 +1451,7 @@ static void als_session_create(tritd_als_session** out, int32_t device, const do
     const int dev = pick_device(device);
     auto* s = new AlsSession(dev, X, ldX, n1, n2, n3, i0, i1, r,
                              opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0, comm,
-                             flags, nullptr, false, observed, holdout, patience, ncvx, val_norm);
+                             flags, nullptr, false, observed, ho, ncvx);
     s->set_quiet(quiet != 0);
     *out = reinterpret_cast<tritd_als_session*>(s);
 }
@@ -1482,7 +1463,7 @@ tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t de
                                              const double* A0, const double* B0, const double* C0,
                                              tritd_comm* comm, uint32_t flags, int32_t quiet) {
     return guarded([&] {
-        als_session_create(out, device, X, observed, nullptr, 0, ldX, n1, n2, n3, i0, i1, r, opts, A0,
+        als_session_create(out, device, X, observed, {}, ldX, n1, n2, n3, i0, i1, r, opts, A0,
                            B0, C0, comm, flags, quiet);
     });
 }
@@ -1499,8 +1480,8 @@ tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t d
         *out = nullptr;
         need(holdout, "holdout");
         if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        als_session_create(out, device, X, observed, holdout, patience, ldX, n1, n2, n3, i0, i1, r,
-                           opts, A0, B0, C0, comm, flags, quiet);
+        als_session_create(out, device, X, observed, {holdout, patience, 2}, ldX, n1, n2, n3, i0, i1,
+                           r, opts, A0, B0, C0, comm, flags, quiet);
     });
 }
 
@@ -1518,8 +1499,8 @@ tritd_status tritd_als_session_create_ncvx_holdout(
         if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
         if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
         const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
-        als_session_create(out, device, X, observed, holdout, patience, ldX, n1, n2, n3, i0, i1, r,
-                           opts, A0, B0, C0, comm, flags, quiet, &np, val_norm);
+        als_session_create(out, device, X, observed, {holdout, patience, val_norm}, ldX, n1, n2, n3,
+                           i0, i1, r, opts, A0, B0, C0, comm, flags, quiet, &np);
     });
 }
 
@@ -1531,7 +1512,7 @@ tritd_status tritd_als_session_get_val2(tritd_als_session* s, double* valHist, d
         if (!as->ncvx_holdout())
             throw Error(TRITD_ERR_STATE, "get_val2: not a nonconvex holdout session");
         int bi = 0, sr = 0;
-        as->get_val(valHist, &bi, &sr, valHist1);
+        as->get_val(valHist, valHist1, &bi, &sr);
         if (best_iter) *best_iter = bi;
         if (stop_reason) *stop_reason = sr;
     });
@@ -1562,7 +1543,7 @@ tritd_status tritd_als_session_get_val(tritd_als_session* s, double* valHist, in
     return guarded([&] {
         need(s, "session");
         int bi = 0, sr = 0;
-        reinterpret_cast<AlsSession*>(s)->get_val(valHist, &bi, &sr);
+        reinterpret_cast<AlsSession*>(s)->get_val(valHist, nullptr, &bi, &sr);
         if (best_iter) *best_iter = bi;
         if (stop_reason) *stop_reason = sr;
     });

@@ -58,6 +58,31 @@ inline void hip_quiet(hipError_t e) {
                                                     hipGetErrorString(e_));                  \
     } while (0)
 
+// A device buffer of doubles; freed on destruction.
+struct DBuf {
+    double* p = nullptr;
+    size_t n = 0;
+    bool owned = true;  // false: a view into another DBuf
+    DBuf() = default;
+    DBuf(const DBuf&) = delete;
+    DBuf& operator=(const DBuf&) = delete;
+    ~DBuf() {
+        if (p && owned) hip_quiet(hipFree(p));
+    }
+    void alloc(size_t count) {
+        n = count;
+        TRITD_HIP(hipMalloc(&p, (count ? count : 1) * sizeof(double)));
+    }
+    void alloc_bytes(size_t bytes) { alloc((bytes + sizeof(double) - 1) / sizeof(double)); }
+    void release() {
+        if (p && owned) hip_quiet(hipFree(p));
+        p = nullptr;
+        n = 0;
+    }
+    float* f() const { return reinterpret_cast<float*>(p); }
+    size_t bytes() const { return n * sizeof(double); }
+};
+
 __host__ __device__ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 __host__ __device__ inline int64_t cdiv(int64_t x, int64_t m) { return (x + m - 1) / m; }
 

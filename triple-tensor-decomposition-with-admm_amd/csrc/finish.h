@@ -68,4 +68,30 @@ __device__ __forceinline__ void reduce_finish_wg(const FinishArgs& f) {
     }
 }
 
+// The two steps the one-thread finish kernels of holdout sessions share
+// (k_holdout.hip, k_als.hip; holdout.h: BestIterate).
+// The running best: iteration k with score v is kept when it is the first or
+// strictly better; hctrl[1] asks the snapshot kernel that follows for its factors.
+__device__ inline void ho_update_best(double v, int k, double* best, int* hctrl) {
+    int snap = 0;
+    if (k == 1 || v < best[0]) {
+        best[0] = v;
+        hctrl[0] = k;
+        snap = 1;
+    }
+    hctrl[1] = snap;
+}
+
+// The stop and its reason: the solver's own convergence test (1) comes before
+// the patience test (2)
+__device__ inline void ho_stop_reason(bool converged, int k, int patience, int* ctrl, int* hctrl) {
+    if (converged) {
+        ctrl[0] = 1;
+        hctrl[2] = 1;
+    } else if (patience > 0 && k - hctrl[0] >= patience) {
+        ctrl[0] = 1;
+        hctrl[2] = 2;
+    }
+}
+
 }  // namespace tritd

@@ -36,6 +36,7 @@
 // The fit path is the MK one on words 0-3; a second accumulator sums
 // (X - Xhat)^2 over the held-out elements (X keeps its value there) into
 // partial[2b + 1], so valHist comes out of the pass that computes errHist.
+#include "finish.h"
 #include "kernels.h"
 
 namespace tritd {
@@ -398,20 +399,9 @@ __global__ void k_als_finish_ho(const double* ss, double Xnorm, double Hnorm, in
     errHist[k - 1] = e;
     valHist[k - 1] = v;
     ctrl[1] = k;
-    int snap = 0;
-    if (k == 1 || v < best[0]) {
-        best[0] = v;
-        hctrl[0] = k;
-        snap = 1;
-    }
-    hctrl[1] = snap;
-    if (k > 1 && fabs(e - errHist[k - 2]) < tol * errHist[k - 2]) {
-        ctrl[0] = 1;
-        hctrl[2] = 1;
-    } else if (patience > 0 && k - hctrl[0] >= patience) {
-        ctrl[0] = 1;
-        hctrl[2] = 2;
-    }
+    ho_update_best(v, k, best, hctrl);
+    ho_stop_reason(k > 1 && fabs(e - errHist[k - 2]) < tol * errHist[k - 2], k, patience, ctrl,
+                   hctrl);
 }
 
 void launch_als_finish_holdout(const double* ss, double Xnorm, double Hnorm, int k, double tol,

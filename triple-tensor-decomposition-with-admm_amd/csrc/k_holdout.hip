@@ -265,20 +265,8 @@ __global__ void k_finish_ho(const double* ss, const double* hs, double normD, do
     const double v2 = sqrt(hs[0]) / Hnorm, v1 = hs[1] / Hsum1;
     valHist[k - 1] = v2;
     valHist1[k - 1] = v1;
-    const double v = val_norm == 1 ? v1 : v2;
-    int snap = 0;
-    if (k == 1 || v < best[0]) {
-        best[0] = v;
-        hctrl[0] = k;
-        snap = 1;
-    }
-    hctrl[1] = snap;
-    if (ctrl[0]) {
-        hctrl[2] = 1;
-    } else if (patience > 0 && k - hctrl[0] >= patience) {
-        ctrl[0] = 1;
-        hctrl[2] = 2;
-    }
+    ho_update_best(val_norm == 1 ? v1 : v2, k, best, hctrl);
+    ho_stop_reason(ctrl[0] != 0, k, patience, ctrl, hctrl);  // (:63 fired in finish_body)
 }
 
 void launch_finish_ho(const double* ss, const double* hs, double normD, double Hnorm, double Hsum1,
@@ -310,14 +298,7 @@ __global__ void k_ncvx_ho_mark(const double* hs, double Hnorm, double Hsum1, int
     const double v2 = sqrt(hs[0]) / Hnorm, v1 = hs[1] / Hsum1;
     valHist[k - 1] = v2;
     valHist1[k - 1] = v1;
-    const double v = val_norm == 1 ? v1 : v2;
-    int snap = 0;
-    if (k == 1 || v < best[0]) {
-        best[0] = v;
-        hctrl[0] = k;
-        snap = 1;
-    }
-    hctrl[1] = snap;
+    ho_update_best(val_norm == 1 ? v1 : v2, k, best, hctrl);
 }
 
 void launch_ncvx_ho_mark(const double* hs, double Hnorm, double Hsum1, int k, int val_norm,
@@ -337,13 +318,8 @@ __global__ void k_ncvx_ho_finish(const double* ss, double Xnorm, int k, double t
     const double e = sqrt(ss[0]) / Xnorm;
     errHist[k - 1] = e;
     ctrl[1] = k;
-    if (k > 1 && fabs(e - errHist[k - 2]) < tol * errHist[k - 2]) {
-        ctrl[0] = 1;
-        hctrl[2] = 1;
-    } else if (patience > 0 && k - hctrl[0] >= patience) {
-        ctrl[0] = 1;
-        hctrl[2] = 2;
-    }
+    ho_stop_reason(k > 1 && fabs(e - errHist[k - 2]) < tol * errHist[k - 2], k, patience, ctrl,
+                   hctrl);
 }
 
 void launch_ncvx_ho_finish(const double* ss, double Xnorm, int k, double tol, int patience,

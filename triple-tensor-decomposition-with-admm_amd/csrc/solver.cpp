@@ -88,13 +88,22 @@ void unpack_C(const Geom& g, const std::vector<double>& Ch, double* C) {
         for (int k = 0; k < g.R; ++k) C[k + (int64_t)g.R * t] = Ch[t * g.RP + k];
 }
 
+void download_factor(const Geom& g, const double* dev, size_t n,
+                     void (*unpack)(const Geom&, const std::vector<double>&, double*), double* out) {
+    if (!out) return;
+    std::vector<double> h(n);
+    TRITD_HIP(hipMemcpy(h.data(), dev, n * sizeof(double), hipMemcpyDeviceToHost));
+    unpack(g, h, out);
+}
+
 // ---------------------------------------------------------------------------
 Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3,
                  int64_t i0, int64_t i1, int r, const tritd_opts& o, const double* A0,
                  const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
                  hipStream_t shared_stream, bool defer_normD, const uint8_t* observed,
-                 const uint8_t* holdout, int patience, int val_norm)
-    : device_(device), o_(o), comm_(comm), patience_(patience), val_norm_(val_norm) {
+                 const HoldoutSpec& ho)
+    : device_(device), o_(o), comm_(comm) {
+    const uint8_t* holdout = ho.mask;
     TRITD_HIP(hipSetDevice(device_));
     g_ = make_geom(n1, n2, n3, i0, i1, r);
     f32_ = (flags & TRITD_SESSION_F32) != 0;
@@ -103,8 +112,8 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     if (holdout) {
         if (o_.model == TRITD_MODEL_QI)  // (the Qi K5 launch carries its own fused finish)
             throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not implemented for opts.model='qi'");
-        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+        if (ho.patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+        if (ho.val_norm != 1 && ho.val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
         holdout_ = true;
     }
     probe_ = (flags & TRITD_SESSION_PROBE) != 0;
@@ -261,17 +270,8 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     TRITD_HIP(hipMalloc(&ctrl_, ctrl_bytes));
     TRITD_HIP(hipMemsetAsync(ctrl_, 0, ctrl_bytes, st_));
     if (holdout_) {
-        valHist_.alloc(mi);
-        valHist1_.alloc(mi);
-        hbest_.alloc(1);
-        hopart_.alloc(2 * (size_t)ho_score_grid(g_));
-        Abest_.alloc(AhB_[0].n);
-        Bbest_.alloc(Bh_.n);
-        Cbest_.alloc(Ch_.n);
-        for (DBuf* b : {&valHist_, &valHist1_, &hbest_})
-            TRITD_HIP(hipMemsetAsync(b->p, 0, b->n * sizeof(double), st_));
-        TRITD_HIP(hipMalloc(&hctrl_, 4 * sizeof(int)));
-        TRITD_HIP(hipMemsetAsync(hctrl_, 0, 4 * sizeof(int), st_));
+        hset_.alloc(g_);
+        val_.alloc(mi, /*l1=*/true, AhB_[0].n, Bh_.n, Ch_.n, ho, st_);
     }
 
     // D -> tile-major device layout (one-off)
@@ -297,11 +297,7 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
             pack_mask(observed, ldD, (flags & TRITD_SESSION_D_ON_DEVICE) != 0, holdout);
     }
     upload_factors(A0, B0, C0);
-    if (holdout_) {  // best_iter = 0 until the first iteration: A0, B0, C0
-        TRITD_HIP(hipMemcpy(Abest_.p, Ah_.p, Abest_.bytes(), hipMemcpyDeviceToDevice));
-        TRITD_HIP(hipMemcpy(Bbest_.p, Bh_.p, Bbest_.bytes(), hipMemcpyDeviceToDevice));
-        TRITD_HIP(hipMemcpy(Cbest_.p, Ch_.p, Cbest_.bytes(), hipMemcpyDeviceToDevice));
-    }
+    if (holdout_) val_.seed(Ah_.p, Bh_.p, Ch_.p);
 
     // normD = norm(D(:))  (:28)
     const int nb = sumsq_blocks(g_);
@@ -313,7 +309,7 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     if (masked_ || holdout_)  // the observed count rides beside normD^2 (summed over the shards)
         TRITD_HIP(hipMemcpyAsync(red3_.p + 1, &obs_count_d_, sizeof(double), hipMemcpyHostToDevice, st_));
     if (holdout_)  // and ||H o Omega o D||^2, the held-out count, sum |H o Omega o D|
-        TRITD_HIP(hipMemcpyAsync(red3_.p + 2, ho_sums_, 3 * sizeof(double), hipMemcpyHostToDevice, st_));
+        TRITD_HIP(hipMemcpyAsync(red3_.p + 2, hset_.sums, sizeof hset_.sums, hipMemcpyHostToDevice, st_));
     if (!defer_normD) {
         allreduce(red3_.p, norm_count());
         set_normD_from_red3();
@@ -370,7 +366,6 @@ Session::~Session() {
         if (e) hip_quiet(hipEventDestroy(e));
     for (auto e : ev_) hip_quiet(hipEventDestroy(e));
     if (ctrl_) hip_quiet(hipFree(ctrl_));
-    if (hctrl_) hip_quiet(hipFree(hctrl_));
     if (own_stream_ && st_) hip_quiet(hipStreamDestroy(st_));
 }
 
@@ -379,90 +374,40 @@ void Session::set_normD_from_red3() {
     TRITD_HIP(hipMemcpyAsync(ss, red3_.p, norm_count() * sizeof(double), hipMemcpyDeviceToHost, st_));
     TRITD_HIP(hipStreamSynchronize(st_));
     normD_ = std::sqrt(ss[0]);
-    if ((masked_ || holdout_) && ss[1] == 0.0)
-        throw Error(TRITD_ERR_ARG, holdout_ ? "no observed entry is left to fit beside the holdout"
-                                            : "observed has no true entry: nothing to fit");
+    check_creation_sums(ss, masked_, holdout_, "D");
     if (holdout_) {
-        Hnorm_ = std::sqrt(ss[2]);
-        Hsum1_ = ss[4];
-        if (ss[3] == 0.0) throw Error(TRITD_ERR_ARG, "holdout has no observed entry: nothing to score");
-        if (ss[2] == 0.0) throw Error(TRITD_ERR_ARG, "the held-out entries of D are all zero");
+        val_.Hnorm = std::sqrt(ss[2]);
+        val_.Hsum1 = ss[4];
         // (the per-iteration sums reuse red3_[2..3])
         TRITD_HIP(hipMemsetAsync(red3_.p, 0, red3_.bytes(), st_));
     }
     if (f32_) normD_ = (double)(float)normD_;  // norm of a single array is single
 }
 
-// opts.observed -> M_ (and D zeroed where unobserved).  A host mask is staged
-// as a contiguous n1l x n2 x n3 byte array first; TRITD_OBSERVED_NAN has no
-// array: the packers read the mask off D_ itself.
+// opts.observed -> M_ (and D zeroed where unobserved); TRITD_OBSERVED_NAN has
+// no array: the packers read the mask off D_ itself.
 // holdout (or null): a second byte mask of the same layout; M_ then holds the
-// fit words Omega & ~H, and Hw_, hoff_, hvals_ the held-out set (k_holdout.hip).
+// fit words Omega & ~H, and hset_ the held-out set (k_holdout.hip).
 void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
                         const uint8_t* holdout) {
     masked_ = true;
-    const int64_t ntiles = g_.Ntm / 256;
-    M_.alloc_bytes((size_t)ntiles * MK_WORDS * sizeof(unsigned long long));
-    DBuf cnt, stage, stageh;
-    cnt.alloc(1);
-    TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
-    const uint8_t* src = observed;
-    const uint8_t* srch = holdout;
-    int64_t ld = ldD;
-    if (!on_device) {
-        const size_t rows = (size_t)(g_.n2 * g_.n3);
-        auto to_device = [&](DBuf& b, const uint8_t* m) {
-            b.alloc_bytes((size_t)g_.n1l * rows);
-            if (ldD == g_.n1l)
-                TRITD_HIP(hipMemcpyAsync(b.p, m, (size_t)g_.n1l * rows, hipMemcpyHostToDevice, st_));
-            else
-                TRITD_HIP(hipMemcpy2DAsync(b.p, (size_t)g_.n1l, m, (size_t)ldD, (size_t)g_.n1l, rows,
-                                           hipMemcpyHostToDevice, st_));
-            return reinterpret_cast<const uint8_t*>(b.p);
-        };
-        if (observed && !obs_is_nan(observed)) src = to_device(stage, observed);
-        if (holdout) srch = to_device(stageh, holdout);
-        ld = g_.n1l;
-    }
+    M_.alloc_bytes((size_t)(g_.Ntm / 256) * MK_WORDS * sizeof(unsigned long long));
+    const StagedMasks m(g_, observed, holdout, ldD, on_device, st_);
     unsigned long long* M = reinterpret_cast<unsigned long long*>(M_.p);
     if (holdout) {
-        // words and per-tile counts, the offsets by a scan, then the compact
-        // values (their number is known only after the scan) and D zeroed
-        // outside the fit mask; the two sums of the values in a fixed order
-        DBuf tcnt, vpart, vsum;
-        Hw_.alloc_bytes((size_t)ntiles * MK_WORDS * sizeof(unsigned long long));
-        hoff_.alloc((size_t)ntiles + 1);
-        tcnt.alloc_bytes((size_t)ntiles * sizeof(unsigned));
-        unsigned long long* Hw = reinterpret_cast<unsigned long long*>(Hw_.p);
-        unsigned long long* hoff = reinterpret_cast<unsigned long long*>(hoff_.p);
-        launch_ho_pack_words(g_, src, srch, ld, D_.p, M, Hw, reinterpret_cast<unsigned*>(tcnt.p),
-                             reinterpret_cast<unsigned long long*>(cnt.p), st_);
-        launch_ho_scan(reinterpret_cast<const unsigned*>(tcnt.p), ntiles, hoff, st_);
-        unsigned long long nh = 0;
-        TRITD_HIP(hipMemcpyAsync(&nh, hoff + ntiles, sizeof nh, hipMemcpyDeviceToHost, st_));
-        TRITD_HIP(hipStreamSynchronize(st_));
-        ho_count_ = (int64_t)nh;
-        hvals_.alloc((size_t)nh);
-        launch_ho_pack_vals(g_, M, Hw, hoff, D_.p, hvals_.p, st_);
-        const int nb = ho_sum_blocks(ho_count_);
-        vpart.alloc(2 * (size_t)nb);
-        vsum.alloc(2);
-        launch_ho_valsum(hvals_.p, ho_count_, vpart.p, nb, st_);
-        launch_reduce_pairs(vpart.p, nb, vsum.p, nullptr, st_);
-        double hs[2] = {0.0, 0.0};
-        TRITD_HIP(hipMemcpyAsync(hs, vsum.p, sizeof hs, hipMemcpyDeviceToHost, st_));
-        TRITD_HIP(hipStreamSynchronize(st_));
-        ho_sums_[0] = hs[0];
-        ho_sums_[1] = (double)nh;
-        ho_sums_[2] = hs[1];
+        obs_count_ = hset_.pack(g_, m.obs, m.hold, m.ld, D_.p, M, st_);
+        val_.count = hset_.count;
     } else {
-        launch_mask_pack(g_, src, ld, M, D_.p, reinterpret_cast<unsigned long long*>(cnt.p), st_);
+        DBuf cnt;
+        cnt.alloc(1);
+        TRITD_HIP(hipMemsetAsync(cnt.p, 0, sizeof(double), st_));
+        launch_mask_pack(g_, m.obs, m.ld, M, D_.p, reinterpret_cast<unsigned long long*>(cnt.p), st_);
+        unsigned long long c = 0;
+        TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
+        TRITD_HIP(hipStreamSynchronize(st_));
+        obs_count_ = (int64_t)c;
     }
-    unsigned long long c = 0;
-    TRITD_HIP(hipMemcpyAsync(&c, cnt.p, sizeof c, hipMemcpyDeviceToHost, st_));
-    TRITD_HIP(hipStreamSynchronize(st_));
-    obs_count_ = (int64_t)c;
-    obs_count_d_ = (double)c;
+    obs_count_d_ = (double)obs_count_;
 }
 
 void Session::upload_factors(const double* A0, const double* B0, const double* C0) {
@@ -866,7 +811,7 @@ void Session::agree_counts() {
     constexpr int NQ = 6;
     const double c[NQ] = {(double)k5n(), (double)red1_count(), (double)red2_count(),
                           (double)o_.maxIter, (double)(o_.disp != 0),
-                          holdout_ ? 1.0 + 4.0 * patience_ + val_norm_ : 0.0};
+                          holdout_ ? 1.0 + 4.0 * val_.patience + val_.val_norm : 0.0};
     double h[2 * NQ];
     for (int q = 0; q < NQ; ++q) {
         h[2 * q] = c[q];
@@ -1287,22 +1232,17 @@ void Session::iterate_sharded(int k) {
 // The score of a holdout iteration, after its K5: T holds L_k outside the fit
 // mask.  sums[0..1] = sum d^2, sum |d| over the shard's held-out entries.
 void Session::holdout_score(double* sums) {
-    const unsigned long long* Hw = reinterpret_cast<const unsigned long long*>(Hw_.p);
-    const unsigned long long* hoff = reinterpret_cast<const unsigned long long*>(hoff_.p);
-    mark(EV_HO);
-    launch_ho_score(g_, T_.p, Hw, hoff, hvals_.p, hopart_.p, ctrl_, st_);
-    mark(EV_HO + 1);
-    launch_reduce_pairs(hopart_.p, ho_score_grid(g_), sums, ctrl_, st_);
+    hset_.score(g_, T_.p, sums, ctrl_, st_, ev_slot(EV_HO), ev_slot(EV_HO + 1));
 }
 
 // errHist(k) and the stop test of :63 as without a holdout, then the scores,
 // the running best and the patience test; the factors of iteration k are kept
 // when it is the best so far (A^ of iteration k is the current parity buffer)
 void Session::holdout_finish(int k, const double* ss, const double* hs) {
-    launch_finish_ho(ss, hs, normD_, Hnorm_, Hsum1_, k, o_.tol, patience_, val_norm_, errHist_.p,
-                     errL_.p, errO_.p, valHist_.p, valHist1_.p, ctrl_, hctrl_, hbest_.p, st_);
-    launch_als_snapshot(Ah_.p, Bh_.p, Ch_.p, Abest_.p, Bbest_.p, Cbest_.p, (int64_t)Abest_.n,
-                        (int64_t)Bbest_.n, (int64_t)Cbest_.n, hctrl_, st_);
+    launch_finish_ho(ss, hs, normD_, val_.Hnorm, val_.Hsum1, k, o_.tol, val_.patience, val_.val_norm,
+                     errHist_.p, errL_.p, errO_.p, val_.valHist.p, val_.valHist1.p, ctrl_, val_.hctrl,
+                     val_.hbest.p, st_);
+    val_.snapshot(Ah_.p, Bh_.p, Ch_.p, st_);
 }
 
 // The end of a holdout iteration on the fused and overlapped schedules: the
@@ -1420,8 +1360,8 @@ void Session::harvest_timing() {
             float sc = 0, tl = 0;
             TRITD_HIP(hipEventElapsedTime(&sc, ev_[b + EV_HO], ev_[b + EV_HO + 1]));
             TRITD_HIP(hipEventElapsedTime(&tl, ev_[b + 4], ev_[b + 5]));
-            acc_score_ += sc;
-            acc_tail_ += tl;
+            val_.acc_score += sc;
+            val_.acc_tail += tl;
         }
         acc_it_ += it;
         acc_m3_ += m3;
@@ -1449,14 +1389,12 @@ void Session::sync(int* done, int* stopped) {
 }
 
 void Session::mark(int slot) {
-    if (!timing_) return;
-    hipEvent_t e = ev_[ev_.size() - EV_SLOTS + slot];
-    if (e) TRITD_HIP(hipEventRecord(e, st_));
+    if (hipEvent_t e = ev_slot(slot)) TRITD_HIP(hipEventRecord(e, st_));
 }
 
 void Session::set_timing(int level) {
     timing_ = level;
-    acc_k5_ = acc_m3_ = acc_it_ = acc_ar_ = acc_score_ = acc_tail_ = 0;
+    acc_k5_ = acc_m3_ = acc_it_ = acc_ar_ = val_.acc_score = val_.acc_tail = 0;
     acc_n_ = ar_per_iter_ = 0;
 }
 
@@ -1478,22 +1416,10 @@ void Session::get(double* A, double* B, double* C, void* O, void* E, int64_t ldO
                   double* errHist, int* iters, bool populated) {
     int done = 0, stopped = 0;
     sync(&done, &stopped);
-    if (A) {  // the A of the last finished iteration (its parity buffer)
-        std::vector<double> h(AhB_[done & 1].n);
-        TRITD_HIP(hipMemcpy(h.data(), finished_ah(done), h.size() * sizeof(double),
-                            hipMemcpyDeviceToHost));
-        unpack_A(g_, h, A);
-    }
-    if (B) {
-        std::vector<double> h(Bh_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Bh_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_B(g_, h, B);
-    }
-    if (C) {
-        std::vector<double> h(Ch_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Ch_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_C(g_, h, C);
-    }
+    // the A of the last finished iteration (its parity buffer)
+    download_factor(g_, finished_ah(done), AhB_[done & 1].n, unpack_A, A);
+    download_factor(g_, Bh_.p, Bh_.n, unpack_B, B);
+    download_factor(g_, Ch_.p, Ch_.n, unpack_C, C);
     if (O && g_.n1l > 0 && done > 0) {  // O of iteration `done` from D, Y_L, T (K5 does not store it)
         if (f32_)
             launch_o_fixup32(g_, D_.f(), YL_.f(), T_.f(), (float)(1.0 / mu_[(size_t)done]), O_.f(),
@@ -1564,38 +1490,16 @@ void Session::get(double* A, double* B, double* C, void* O, void* E, int64_t ldO
 }
 
 void Session::get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason) {
-    int done = 0, stopped = 0;
-    sync(&done, &stopped);
+    int done = 0;
+    sync(&done, nullptr);
     if (!holdout_) throw Error(TRITD_ERR_STATE, "get_val: not a holdout session");
-    int h[3];
-    TRITD_HIP(hipMemcpy(h, hctrl_, sizeof h, hipMemcpyDeviceToHost));
-    if (valHist && done > 0)
-        TRITD_HIP(hipMemcpy(valHist, valHist_.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
-    if (valHist1 && done > 0)
-        TRITD_HIP(hipMemcpy(valHist1, valHist1_.p, (size_t)done * sizeof(double), hipMemcpyDeviceToHost));
-    if (best_iter) *best_iter = h[0];
-    if (stop_reason) *stop_reason = h[2];
+    val_.get_val(done, valHist, valHist1, best_iter, stop_reason);
 }
 
 void Session::get_best(double* A, double* B, double* C) {
-    int done = 0, stopped = 0;
-    sync(&done, &stopped);
+    sync(nullptr, nullptr);
     if (!holdout_) throw Error(TRITD_ERR_STATE, "get_best: not a holdout session");
-    if (A) {
-        std::vector<double> h(Abest_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Abest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_A(g_, h, A);
-    }
-    if (B) {
-        std::vector<double> h(Bbest_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Bbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_B(g_, h, B);
-    }
-    if (C) {
-        std::vector<double> h(Cbest_.n);
-        TRITD_HIP(hipMemcpy(h.data(), Cbest_.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-        unpack_C(g_, h, C);
-    }
+    val_.get_best(g_, A, B, C);
 }
 
 void Session::counters(int64_t* dense_tiles_total, int64_t* tiles_per_launch) {

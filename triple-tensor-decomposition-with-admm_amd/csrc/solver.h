@@ -7,6 +7,7 @@
 #include <thread>
 #include <vector>
 
+#include "holdout.h"
 #include "kernels.h"
 
 namespace tritd {
@@ -54,31 +55,6 @@ private:
 // ordered on stream st: ncclAllReduce, or the host transport (drains st).
 void comm_allreduce(tritd_comm* c, double* buf, int64_t count, bool max, hipStream_t st);
 
-// A device buffer of doubles; freed on destruction.
-struct DBuf {
-    double* p = nullptr;
-    size_t n = 0;
-    bool owned = true;  // false: a view into another DBuf
-    DBuf() = default;
-    DBuf(const DBuf&) = delete;
-    DBuf& operator=(const DBuf&) = delete;
-    ~DBuf() {
-        if (p && owned) hip_quiet(hipFree(p));
-    }
-    void alloc(size_t count) {
-        n = count;
-        TRITD_HIP(hipMalloc(&p, (count ? count : 1) * sizeof(double)));
-    }
-    void alloc_bytes(size_t bytes) { alloc((bytes + sizeof(double) - 1) / sizeof(double)); }
-    void release() {
-        if (p && owned) hip_quiet(hipFree(p));
-        p = nullptr;
-        n = 0;
-    }
-    float* f() const { return reinterpret_cast<float*>(p); }
-    size_t bytes() const { return n * sizeof(double); }
-};
-
 // Host-side layout conversions between the reference shapes and the device
 // factor layout (common.h / DESIGN.md §3).
 void pack_A(const Geom& g, const double* A, std::vector<double>& Ah, std::vector<double>& AhT);
@@ -87,6 +63,9 @@ void pack_C(const Geom& g, const double* C, std::vector<double>& Ch, std::vector
 void unpack_A(const Geom& g, const std::vector<double>& Ah, double* A);
 void unpack_B(const Geom& g, const std::vector<double>& Bh, double* B);
 void unpack_C(const Geom& g, const std::vector<double>& Ch, double* C);
+// the n doubles of a device factor through unpack_A/B/C into out (null: nothing)
+void download_factor(const Geom& g, const double* dev, size_t n,
+                     void (*unpack)(const Geom&, const std::vector<double>&, double*), double* out);
 
 class Session {
    public:
@@ -95,7 +74,7 @@ class Session {
             int64_t i1, int r, const tritd_opts& o, const double* A0, const double* B0,
             const double* C0, tritd_comm* comm, uint32_t flags, hipStream_t shared_stream = nullptr,
             bool defer_normD = false, const uint8_t* observed = nullptr,
-            const uint8_t* holdout = nullptr, int patience = 0, int val_norm = 2);
+            const HoldoutSpec& ho = {});
     ~Session();
 
     // Enqueue iterations (full collective schedule; used without a virtual group)
@@ -129,9 +108,7 @@ class Session {
     bool holdout() const { return holdout_; }
     // held-out entries of the shard; ||H o Omega o D|| and sum |.| over all shards
     void holdout_info(int64_t* count, double* norm, double* sum1) const {
-        if (count) *count = ho_count_;
-        if (norm) *norm = Hnorm_;
-        if (sum1) *sum1 = Hsum1_;
+        val_.info(count, norm, sum1);
     }
     // valHist, valHist1 (as many entries as errHist), best_iter, stop_reason
     void get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason);
@@ -139,11 +116,7 @@ class Session {
     void get_best(double* A, double* B, double* C);
     // ms per timed iteration (TRITD_TIMING_ALL) in the score kernel, and from
     // the end of K5 to the end of the iteration (score, reductions, finish, snapshot)
-    void holdout_ms(double* score, double* tail) const {
-        const double n = acc_n_ ? (double)acc_n_ : 1.0;
-        if (score) *score = acc_score_ / n;
-        if (tail) *tail = acc_tail_ / n;
-    }
+    void holdout_ms(double* score, double* tail) const { val_.holdout_ms(acc_n_, score, tail); }
     // doubles of red3 reduced over the shards at creation (normD^2, the fit
     // count; holdout: + ||H o Omega o D||^2, the held-out count, sum |.|) and in
     // every iteration of the phase schedules (holdout: + the two score sums)
@@ -272,18 +245,12 @@ class Session {
     }
     void pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
                    const uint8_t* holdout = nullptr);
-    // holdout=: M_ holds the fit words Omega & ~H; Hw_ the words of H & Omega,
-    // hoff_ the tiles' offsets into hvals_, the compact held-out values
-    // (k_holdout.hip).  red3_[2..3] carry the score sums of an iteration.
-    // Control words of their own: hctrl_[0] best_iter, [1] snapshot request,
-    // [2] stop_reason; hbest_[0] = the best score so far.
+    // holdout=: M_ holds the fit words Omega & ~H, hset_ the held-out set and
+    // val_ the validation state (holdout.h).  red3_[2..3] carry the score sums
+    // of an iteration.
     bool holdout_ = false;
-    int patience_ = 0, val_norm_ = 2;
-    int64_t ho_count_ = 0;
-    double Hnorm_ = 0.0, Hsum1_ = 0.0;
-    double ho_sums_[3] = {0.0, 0.0, 0.0};  // creation: ||.||^2, count, sum |.| of the shard
-    int* hctrl_ = nullptr;
-    DBuf Hw_, hoff_, hvals_, hopart_, valHist_, valHist1_, hbest_, Abest_, Bbest_, Cbest_;
+    HoldoutSet hset_;
+    BestIterate val_;
     // the end of a holdout iteration: score, norm reduction, finish, snapshot
     // (holdout_tail: the fused and overlapped schedules; the phase schedules
     // call holdout_score after K5 and holdout_finish as their phase D)
@@ -339,7 +306,11 @@ class Session {
     }
 
     int timing_ = 0;
-    void mark(int slot);  // record timing event `slot` of this iteration (if it exists)
+    // timing event `slot` of this iteration (null: not timed), and its record
+    hipEvent_t ev_slot(int slot) const {
+        return timing_ ? ev_[ev_.size() - EV_SLOTS + slot] : nullptr;
+    }
+    void mark(int slot);
     // per timed iteration: EV_SLOTS events — 0 start, 1/2 K2, 3/4 K5, 5 end,
     // then a (before, after) pair per all-reduce of the iteration
     static constexpr int EV_AR = 4;  // all-reduce pairs timed per iteration
@@ -348,7 +319,7 @@ class Session {
     std::vector<hipEvent_t> ev_;
     std::vector<int> ev_iter_;
     int ar_in_iter_ = 0;  // all-reduces issued so far in the current iteration
-    double acc_k5_ = 0, acc_m3_ = 0, acc_it_ = 0, acc_ar_ = 0, acc_score_ = 0, acc_tail_ = 0;
+    double acc_k5_ = 0, acc_m3_ = 0, acc_it_ = 0, acc_ar_ = 0;
     int acc_n_ = 0, ar_per_iter_ = 0;
     void harvest_timing();
 };
