@@ -20,34 +20,30 @@ namespace tritd {
 
 void emit_line(const char* line);  // api.cpp
 
-AlsSession::AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int64_t n2,
-                       int64_t n3, int64_t i0, int64_t i1, int r, int maxIter, double tol,
-                       const double* A0, const double* B0, const double* C0, tritd_comm* comm,
-                       uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                       const uint8_t* observed, const HoldoutSpec& ho, const NcvxParams* ncvx)
+// (the argument rules — patience, val_norm, rho — are api.cpp's: every
+// construction passes them first)
+AlsSession::AlsSession(int device, const ShardInputs& in, int maxIter, double tol,
+                       const NcvxParams* ncvx, tritd_comm* comm, hipStream_t shared_stream,
+                       bool defer_norm)
     : device_(device), maxIter_(maxIter < 0 ? 0 : maxIter), tol_(tol), comm_(comm) {
-    if (ho.mask && ho.patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-    if (ncvx && !ho.mask)
+    if (ncvx && !in.ho.mask)
         throw Error(TRITD_ERR_ARG, "a nonconvex session without a holdout is made by enable_ncvx");
-    if (ncvx && ho.val_norm != 1 && ho.val_norm != 2)
-        throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
-    if (ncvx && !(ncvx->rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
     try {  // (a constructor that throws runs no destructor: an all-false mask is refused here)
-        init(X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, flags, shared_stream, defer_norm, observed,
-             ho, ncvx);
+        init(in, ncvx, shared_stream, defer_norm);
     } catch (...) {
         release();
         throw;
     }
 }
 
-void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
-                      int64_t i1, int r, const double* A0, const double* B0, const double* C0,
-                      uint32_t flags, hipStream_t shared_stream, bool defer_norm,
-                      const uint8_t* observed, const HoldoutSpec& ho, const NcvxParams* ncvx) {
-    const uint8_t* holdout = ho.mask;
+void AlsSession::init(const ShardInputs& in, const NcvxParams* ncvx, hipStream_t shared_stream,
+                      bool defer_norm) {
+    const double* X = static_cast<const double*>(in.D);
+    const int64_t ldX = in.ld, n2 = in.n2, n3 = in.n3;
+    const uint32_t flags = in.flags;
+    const uint8_t *observed = in.observed, *holdout = in.ho.mask;
     TRITD_HIP(hipSetDevice(device_));
-    g_ = make_geom(n1, n2, n3, i0, i1, r);
+    g_ = make_geom(in.n1, n2, n3, in.i0, in.i1, in.r);
     hoscore_ = holdout && ncvx;
     if (!rp_supported(g_.RP))
         throw Error(TRITD_ERR_UNSUPPORTED, "r must be in 1..8 for the fp64 ALS path");
@@ -92,7 +88,7 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     TRITD_HIP(hipMemsetAsync(ctrl_, 0, 4 * sizeof(int), st_));
     if (holdout) {
         holdout_ = true;
-        val_.alloc(errHist_.n, /*l1=*/hoscore_, Ah_.n, Bh_.n, Ch_.n, ho, st_);
+        val_.alloc(errHist_.n, /*l1=*/hoscore_, Ah_.n, Bh_.n, Ch_.n, in.ho, st_);
         if (hoscore_) hset_.alloc(g_);
     }
 
@@ -123,9 +119,9 @@ void AlsSession::init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int6
     if (!masked_) launch_tm_to_tx(g_, X_.p, XT_.p, st_);
 
     std::vector<double> Ah, AhT, Bh, Ch, ChT;
-    pack_A(g_, A0, Ah, AhT);
-    pack_B(g_, B0, Bh);
-    pack_C(g_, C0, Ch, ChT);
+    pack_A(g_, in.A0, Ah, AhT);
+    pack_B(g_, in.B0, Bh);
+    pack_C(g_, in.C0, Ch, ChT);
     TRITD_HIP(hipMemcpy(Ah_.p, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
     TRITD_HIP(hipMemcpy(AhT_.p, AhT.data(), AhT.size() * sizeof(double), hipMemcpyHostToDevice));
     TRITD_HIP(hipMemcpy(Bh_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -247,7 +243,7 @@ void AlsSession::enable_ncvx(const NcvxParams& p) {
         throw Error(TRITD_ERR_STATE, "the nonconvex solver is chosen once, before the first run");
     if (holdout_)
         throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not supported by the nonconvex solver");
-    if (!(p.rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+    p.check();
     start_ncvx(p);
 }
 

@@ -11,22 +11,24 @@ namespace tritd {
 // (positional in the reference: rho, lambda, gamma_A, epsilon, p, theta).
 struct NcvxParams {
     double rho, lambda, gamma_A, epsilon, p, theta;
+    // the one argument rule of the solver (test.m divides by rho)
+    void check() const {
+        if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+    }
 };
 
 class AlsSession {
    public:
-    // X: double, column-major shard rows [i0, i1) with leading dim ldX (host,
-    // or device with TRITD_SESSION_D_ON_DEVICE).  maxIter, tol: the only
+    // in.D: double, column-major shard rows [i0, i1) with leading dim in.ld
+    // (host, or device with TRITD_SESSION_D_ON_DEVICE).  maxIter, tol: the only
     // opts fields the reference reads (triple_decomp_ALS.m:2-3).
-    // observed (or null): the byte mask of the shard, laid out like X (fibres
-    // ldX bytes apart, nonzero = observed; host or device like X).  The
+    // in.observed (or null): the byte mask of the shard, laid out like X (fibres
+    // ld bytes apart, nonzero = observed; host or device like X).  The
     // session then fits the observed entries only (tritd_als_masked_f64).
-    AlsSession(int device, const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3,
-               int64_t i0, int64_t i1, int r, int maxIter, double tol, const double* A0,
-               const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
-               hipStream_t shared_stream = nullptr, bool defer_norm = false,
-               const uint8_t* observed = nullptr, const HoldoutSpec& ho = {},
-               const NcvxParams* ncvx = nullptr);
+    // ncvx: with in.ho only (below); shared_stream, defer_norm as for Session.
+    AlsSession(int device, const ShardInputs& in, int maxIter, double tol,
+               const NcvxParams* ncvx = nullptr, tritd_comm* comm = nullptr,
+               hipStream_t shared_stream = nullptr, bool defer_norm = false);
     ~AlsSession();
     AlsSession(const AlsSession&) = delete;
     AlsSession& operator=(const AlsSession&) = delete;
@@ -163,10 +165,8 @@ class AlsSession {
     bool hoscore_ = false;
     HoldoutSet hset_;
     void start_ncvx(const NcvxParams& p);
-    void init(const double* X, int64_t ldX, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
-              int64_t i1, int r, const double* A0, const double* B0, const double* C0,
-              uint32_t flags, hipStream_t shared_stream, bool defer_norm, const uint8_t* observed,
-              const HoldoutSpec& ho, const NcvxParams* ncvx);
+    void init(const ShardInputs& in, const NcvxParams* ncvx, hipStream_t shared_stream,
+              bool defer_norm);
     void release();  // what the destructor frees beyond the members' own
 };
 

@@ -99,18 +99,68 @@ void check_dims(int64_t n1, int64_t n2, int64_t n3, int32_t r, bool f32 = false)
     if (f32 && r > 16) throw Error(TRITD_ERR_UNSUPPORTED, "r <= 16 (R = r^2 <= 256)");
 }
 
-void need(const void* p, const char* what);
+void need(const void* p, const char* what) {
+    if (!p) throw Error(TRITD_ERR_ARG, std::string(what) + " is NULL");
+}
 
-// the argument rules of tritd_admm_holdout_f64 that need no device
-void check_holdout(const tritd_opts* o, int32_t patience, int32_t val_norm) {
+// The argument rules that need no device, each written here once (rho:
+// NcvxParams::check, als.h).  Every entry point calls the ones that apply to
+// it before its first HIP call, in the order it has always reported them; the
+// session constructors rely on that and carry no copy.
+void rule_patience(int32_t patience) {
     if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
+}
+void rule_val_norm(int32_t val_norm) {
     if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+}
+void rule_holdout_model(const tritd_opts* o) {  // (the Qi K5 launch carries its own fused finish)
     if (o->model == TRITD_MODEL_QI)
         throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not implemented for opts.model='qi'");
 }
+// what: the mask argument in the caller's words ("observed", "holdout")
+void rule_mask_f64(uint32_t flags, const char* what) {
+    if (flags & TRITD_SESSION_F32)
+        throw Error(TRITD_ERR_UNSUPPORTED,
+                    std::string(what) + " (a mask) is implemented for a double D only");
+}
 
-void need(const void* p, const char* what) {
-    if (!p) throw Error(TRITD_ERR_ARG, std::string(what) + " is NULL");
+// dims, then the input pointers, in the order every solving and creating
+// entry point reports them.  data: the tensor in the caller's words ("D",
+// "X"); wide: the ADMM rank limit; holdout: the call takes a holdout mask
+void check_inputs(const ShardInputs& in, const char* data, bool wide, bool holdout) {
+    check_dims(in.n1, in.n2, in.n3, in.r, wide);
+    need(in.D, data);
+    if (holdout) need(in.ho.mask, "holdout");
+    need(in.A0, "A0"); need(in.B0, "B0"); need(in.C0, "C0");
+}
+
+// the shard of a session creator; ld: the leading dimension's name ("ldD", "ldX")
+void check_shard(const ShardInputs& in, const char* ld) {
+    if (in.i0 < 0 || in.i1 > in.n1 || in.i0 >= in.i1) throw Error(TRITD_ERR_ARG, "bad shard range");
+    if (in.ld < in.i1 - in.i0)
+        throw Error(TRITD_ERR_ARG, std::string(ld) + " smaller than the shard");
+}
+
+// a whole n1 x n2 x n3 tensor in the caller's memory: the inputs of a one-shot call
+ShardInputs whole(const void* D, int64_t n1, int64_t n2, int64_t n3, int32_t r, const double* A0,
+                  const double* B0, const double* C0, const uint8_t* observed = nullptr,
+                  const HoldoutSpec& ho = {}, uint32_t flags = 0) {
+    return {D, n1, n1, n2, n3, 0, n1, r, A0, B0, C0, observed, ho, flags};
+}
+
+// a session handle of the C ABI as the object behind it
+Session* admm(tritd_session* s) {
+    need(s, "session");
+    return reinterpret_cast<Session*>(s);
+}
+AlsSession* als(tritd_als_session* s) {
+    need(s, "session");
+    return reinterpret_cast<AlsSession*>(s);
+}
+// an optional output
+template <class T, class V>
+void put(T* out, V v) {
+    if (out) *out = (T)v;
 }
 
 // first HIP use of an entry point: from here on guarded() clears the
@@ -499,110 +549,97 @@ void run_threaded(DeviceGroup& grp, F&& shard) {
     for (int p = 0; p < P; ++p) g_last_flags |= fl[p];
 }
 
-// One ADMM problem sharded along mode 1 over `devs`, driven
-// the way one process per GPU drives it: each shard is a Session with a
-// communicator, stepped by its own host thread through the same schedule
-// bench.py and the multi-rank tests run (the fused single-stream iteration
-// with two all-reduces per iteration, or its side-stream form for fp32 / Qi /
-// r > 8).  Distinct devices all-reduce over RCCL (communicators from
-// group_comms, cached); one device repeated uses the in-process
-// ThreadReducer.  Shard 0 runs on the calling thread, so `disp` prints (the
-// MEX's mexPrintf) stay on the host's own thread.  D, O, E are column-major
-// n1 x n2 x n3 host arrays of es-byte elements.
-// The holdout arguments of the one-shot holdout calls (tritd_admm_holdout_f64,
-// tritd_als_holdout_f64, tritd_ncvx_holdout_f64; every output may be null;
+// The outputs of a one-shot solve, whole arrays in the caller's memory (any
+// may be null).  O, E: elements of the data's type; the ALS writes neither,
+// the nonconvex solver O alone.  ho: the holdout calls' further outputs
+// (tritd_admm_holdout_f64, tritd_als_holdout_f64, tritd_ncvx_holdout_f64;
 // valHist1 is written by the ADMM and the nonconvex solver).
-struct HoldoutArgs {
-    HoldoutSpec spec;
+struct HoldoutOutputs {
     double *A_best, *B_best, *C_best, *valHist, *valHist1;
     int32_t *best_iter, *stop_reason;
 };
-// the spec of the shard that starts at row i0 (none without holdout arguments)
-HoldoutSpec ho_rows(const HoldoutArgs* ho, int64_t i0) {
-    return ho ? ho->spec.rows(i0) : HoldoutSpec{};
+struct SolveOutputs {
+    double *A, *B, *C;
+    void *O, *E;
+    double* errHist;
+    int32_t* iters;
+    const HoldoutOutputs* ho = nullptr;
+};
+
+// Where a one-shot call runs.  as_set: a device set (tritd_set_devices, or the
+// shards of a *_sharded_virtual_f64 call), which alone consults TRITD_SHOV;
+// otherwise one device, already picked.
+struct Target {
+    std::vector<int> devs;
+    bool as_set;
+};
+// the target of a call that names `device` (after the argument checks: the
+// first HIP call of the entry point)
+Target one_shot_target(int32_t device) {
+    if (device < 0 && g_devices.size() > 1) return {g_devices, true};
+    return {{pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device)}, false};
 }
+Target virtual_target(int32_t nshards, int64_t n1, int32_t device) {
+    if (nshards < 1 || nshards > 16 || nshards > n1)
+        throw Error(TRITD_ERR_ARG, "nshards must be in 1..min(16,n1)");
+    return {std::vector<int>((size_t)nshards, pick_device(device)), true};
+}
+// TRITD_SHOV=0: a device set runs the phase-serial order of round 1 (one host
+// thread enqueues every shard's phases, three reductions per iteration)
+bool phase_serial() {
+    const char* sh = std::getenv("TRITD_SHOV");
+    return sh && std::atoi(sh) == 0;
+}
+
+// rows i0.. of a whole column-major output of es-byte elements (null stays null)
+void* rows_of(void* p, int64_t i0, size_t es) { return p ? static_cast<char*>(p) + i0 * es : nullptr; }
 
 // A rows of the best iterate are shard-local, B and C replicated; every
 // shard holds the same histories and decisions (the sums are all-reduced).
 template <class S>
-void get_holdout(S& s, int p, const HoldoutArgs& h) {
+void get_holdout(S& s, int p, const HoldoutOutputs& h) {
     int bi = 0, sr = 0;
     s.get_val(p == 0 ? h.valHist : nullptr, p == 0 ? h.valHist1 : nullptr, &bi, &sr);
     s.get_best(h.A_best, p == 0 ? h.B_best : nullptr, p == 0 ? h.C_best : nullptr);
-    if (p == 0 && h.best_iter) *h.best_iter = bi;
-    if (p == 0 && h.stop_reason) *h.stop_reason = sr;
+    if (p == 0) put(h.best_iter, bi);
+    if (p == 0) put(h.stop_reason, sr);
 }
 
-void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags,
-                      int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
-                      const double* A0, const double* B0, const double* C0, double* A, double* B,
-                      double* C, void* O, void* E, double* errHist, int32_t* iters,
-                      const uint8_t* observed = nullptr, const HoldoutArgs* ho = nullptr);
-
-// observed (or null): the byte mask of tritd_admm_masked_f64, laid out like D
-void run_group(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags, int64_t n1,
-               int64_t n2, int64_t n3, int32_t r, const tritd_opts& o, const double* A0,
-               const double* B0, const double* C0, double* A, double* B, double* C, void* O,
-               void* E, double* errHist, int32_t* iters, const uint8_t* observed = nullptr,
-               const HoldoutArgs* ho = nullptr) {
-    {
-        // TRITD_SHOV=0: the phase-serial order of round 1 (one host thread
-        // enqueues every shard's phases, three reductions per iteration)
-        const char* sh = std::getenv("TRITD_SHOV");
-        if (sh && std::atoi(sh) == 0) {
-            run_group_serial(devs, D, es, flags, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
-                             errHist, iters, observed, ho);
-            return;
-        }
-    }
-    DeviceGroup grp(devs, n1);
-    const int P = grp.size();
-    if (P == 1) {
-        Session s(devs[0], D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, flags, nullptr,
-                  false, observed, ho_rows(ho, 0));
-        OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * es);
-        s.run(o.maxIter);
-        pf.join();
-        int k = 0;
-        s.get(A, B, C, O, E, n1, errHist, &k, true);
-        if (ho) get_holdout(s, 0, *ho);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
-        return;
-    }
-    run_threaded(grp, [&](int p, tritd_comm* comm) {
-        const auto [i0, i1] = grp.rows(p, n1);
-        Session s(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3, i0, i1, r, o, A0,
-                  B0, C0, comm, flags, nullptr, false, obs_rows(observed, i0), ho_rows(ho, i0));
-        s.run(o.maxIter);
-        int k = 0;
-        s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
-              O ? static_cast<char*>(O) + i0 * es : nullptr,
-              E ? static_cast<char*>(E) + i0 * es : nullptr, n1, p == 0 ? errHist : nullptr, &k);
-        if (ho) get_holdout(s, p, *ho);
-        if (p == 0 && iters) *iters = k;
-        return s.flags();
-    });
+// Shard p's part of the outputs after its run: its rows of A, O and E; B, C,
+// errHist, the iteration count and the histories from shard 0.  Returns the
+// shard's TRITD_FLAG_* bits.  populated: Session::get
+uint32_t read_back(Session& s, int p, const ShardInputs& in, const SolveOutputs& out,
+                   bool populated = false) {
+    const int64_t i0 = s.geom().i0;
+    int k = 0;
+    s.get(out.A, p == 0 ? out.B : nullptr, p == 0 ? out.C : nullptr, rows_of(out.O, i0, in.es()),
+          rows_of(out.E, i0, in.es()), in.n1, p == 0 ? out.errHist : nullptr, &k, populated);
+    if (out.ho) get_holdout(s, p, *out.ho);
+    if (p == 0) put(out.iters, k);
+    return s.flags();
+}
+uint32_t read_back(AlsSession& s, int p, const ShardInputs& in, const SolveOutputs& out) {
+    int k = 0;
+    s.get(out.A, p == 0 ? out.B : nullptr, p == 0 ? out.C : nullptr,
+          p == 0 ? out.errHist : nullptr, &k);
+    if (s.ncvx() && out.O) s.get_O(static_cast<double*>(out.O) + s.geom().i0, in.n1);
+    if (out.ho) get_holdout(s, p, *out.ho);
+    if (p == 0) put(out.iters, k);
+    return s.flags();
 }
 
 // The phase-serial schedule (TRITD_SHOV=0): every iteration runs the four
-// phases of solver.cpp on each shard with the three reductions between them.  D, O, E are column-major n1 x n2 x n3 host arrays
-// of es-byte elements.
-void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, uint32_t flags,
-                      int64_t n1, int64_t n2, int64_t n3, int32_t r, const tritd_opts& o,
-                      const double* A0, const double* B0, const double* C0, double* A, double* B,
-                      double* C, void* O, void* E, double* errHist, int32_t* iters,
-                      const uint8_t* observed, const HoldoutArgs* ho) {
-    DeviceGroup grp(devs, n1);
+// phases of solver.cpp on each shard with the three reductions between them.
+void admm_phase_serial(const std::vector<int>& devs, const ShardInputs& in, const tritd_opts& o,
+                       const SolveOutputs& out) {
+    DeviceGroup grp(devs, in.n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<Session>> ss;
     for (int p = 0; p < P; ++p) {
-        const auto [i0, i1] = grp.rows(p, n1);
+        const auto [i0, i1] = grp.rows(p, in.n1);
         TRITD_HIP(hipSetDevice(devs[p]));
-        ss.emplace_back(new Session(devs[p], static_cast<const char*>(D) + i0 * es, n1, n1, n2, n3,
-                                    i0, i1, r, o, A0, B0, C0, nullptr, flags, grp.vst,
-                                    /*defer_normD=*/true, obs_rows(observed, i0),
-                                    ho_rows(ho, i0)));
+        ss.emplace_back(new Session(devs[p], in.shard(i0, i1), o, nullptr, grp.vst,
+                                    /*defer_normD=*/true));
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
     grp.reduce(ss, &Session::red3, ss[0]->norm_count());
@@ -621,84 +658,82 @@ void run_group_serial(const std::vector<int>& devs, const void* D, size_t es, ui
         TRITD_HIP(hipSetDevice(devs[0]));
         ss[0]->maybe_print(k);
     }
-    int k = 0;
     for (int p = 0; p < P; ++p) {
-        const int64_t i0 = ss[p]->geom().i0;
         TRITD_HIP(hipSetDevice(devs[p]));
-        ss[p]->get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr,
-                   O ? static_cast<char*>(O) + i0 * es : nullptr,
-                   E ? static_cast<char*>(E) + i0 * es : nullptr, n1, p == 0 ? errHist : nullptr, &k);
-        if (ho) get_holdout(*ss[p], p, *ho);
-        g_last_flags |= ss[p]->flags();
+        g_last_flags |= read_back(*ss[p], p, in, out);
     }
-    if (iters) *iters = k;
 }
 
-// triple_decomp_ALS over a device set: the ALS phases (als.cpp) with the
-// fit sum, [M2 | A^TA] and M3 reduced between them.
-void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
-                          int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
-                          const double* B0, const double* C0, double* A, double* B, double* C,
-                          double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O,
-                          const uint8_t* observed, const HoldoutArgs* ho);
-
-// triple_decomp_ALS / the test.m solver over a device set: one AlsSession
-// per shard with a communicator (its run() carries the fit-sum, [M2 | A^TA]
-// and M3 all-reduces), one host thread per shard (run_threaded);
-// TRITD_SHOV=0 keeps the phase-serial order (run_als_group_serial).
-// observed (or null): the byte mask of tritd_als_masked_f64, laid out like X.
-void run_als_group(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
-                   int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
-                   const double* B0, const double* C0, double* A, double* B, double* C,
-                   double* errHist, int32_t* iters, const NcvxParams* ncvx = nullptr,
-                   double* O = nullptr, const uint8_t* observed = nullptr,
-                   const HoldoutArgs* ho = nullptr) {
-    {
-        const char* sh = std::getenv("TRITD_SHOV");
-        if (sh && std::atoi(sh) == 0) {
-            run_als_group_serial(devs, X, n1, n2, n3, r, maxIter, tol, A0, B0, C0, A, B, C, errHist,
-                                 iters, ncvx, O, observed, ho);
-            return;
-        }
+// One ADMM problem, the body of every tritd_admm_* one-shot call (its
+// device-set branch was run_group, admm_phase_serial run_group_serial; the
+// ALS pair below run_als_group and run_als_group_serial).  On one
+// device: a Session over the whole tensor, with O and E faulted in beside the
+// iterations (OutputPrefault; this path alone).  On a device set: sharded
+// along mode 1 and driven the way one process per GPU drives
+// it: each shard is a Session with a communicator, stepped by its own host
+// thread through the same schedule bench.py and the multi-rank tests run (the
+// fused single-stream iteration with two all-reduces per iteration, or its
+// side-stream form for fp32 / Qi / r > 8).  Distinct devices all-reduce over
+// RCCL (communicators from group_comms, cached); one device repeated uses the
+// in-process ThreadReducer.  Shard 0 runs on the calling thread, so `disp`
+// prints (the MEX's mexPrintf) stay on the host's own thread.
+void solve_admm(const Target& t, const ShardInputs& in, const tritd_opts& o,
+                const SolveOutputs& out) {
+    if (t.as_set && phase_serial()) return admm_phase_serial(t.devs, in, o, out);
+    if (t.devs.size() == 1) {
+        Session s(t.devs[0], in, o);
+        OutputPrefault pf(out.O, out.E, (size_t)(in.n1 * in.n2 * in.n3) * in.es());
+        s.run(o.maxIter);
+        pf.join();
+        g_last_flags |= read_back(s, 0, in, out, /*populated=*/true);
+        return;
     }
-    DeviceGroup grp(devs, n1);
+    DeviceGroup grp(t.devs, in.n1);
     run_threaded(grp, [&](int p, tritd_comm* comm) {
-        const auto [i0, i1] = grp.rows(p, n1);
-        AlsSession s(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0, B0, C0,
-                     grp.size() > 1 ? comm : nullptr, 0, nullptr, false,
-                     obs_rows(observed, i0), ho_rows(ho, i0), ho ? ncvx : nullptr);
-        if (ncvx && !ho) s.enable_ncvx(*ncvx);
-        s.run(maxIter);
-        int k = 0;
-        s.get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr, p == 0 ? errHist : nullptr, &k);
-        if (ho) get_holdout(s, p, *ho);
-        if (ncvx && O) s.get_O(O + s.geom().i0, n1);
-        if (p == 0 && iters) *iters = k;
-        return s.flags();
+        const auto [i0, i1] = grp.rows(p, in.n1);
+        Session s(t.devs[p], in.shard(i0, i1), o, comm);
+        s.run(o.maxIter);
+        return read_back(s, p, in, out);
     });
 }
 
-void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t n1, int64_t n2,
-                          int64_t n3, int32_t r, int maxIter, double tol, const double* A0,
-                          const double* B0, const double* C0, double* A, double* B, double* C,
-                          double* errHist, int32_t* iters, const NcvxParams* ncvx, double* O,
-                          const uint8_t* observed, const HoldoutArgs* ho) {
-    DeviceGroup grp(devs, n1);
+// maxIter, tol: what triple_decomp_ALS reads of opts; ncvx (or null): the
+// nonconvex solver of test.m instead
+struct AlsParams {
+    int maxIter;
+    double tol;
+    const NcvxParams* ncvx = nullptr;
+};
+AlsParams als_params(const tritd_opts* opts) { return {opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol}; }
+
+// A shard's AlsSession of the one-shot calls: the nonconvex solver with a
+// holdout is chosen at construction, without one by enable_ncvx
+std::unique_ptr<AlsSession> make_als(int dev, const ShardInputs& in, const AlsParams& ap,
+                                     tritd_comm* comm = nullptr, hipStream_t shared = nullptr,
+                                     bool defer_norm = false) {
+    const bool ho = in.ho.mask != nullptr;
+    auto s = std::make_unique<AlsSession>(dev, in, ap.maxIter, ap.tol, ho ? ap.ncvx : nullptr, comm,
+                                          shared, defer_norm);
+    if (ap.ncvx && !ho) s->enable_ncvx(*ap.ncvx);
+    return s;
+}
+
+// TRITD_SHOV=0: the ALS phases (als.cpp) with the fit sum, [M2 | A^TA] and M3
+// reduced between them.
+void als_phase_serial(const std::vector<int>& devs, const ShardInputs& in, const AlsParams& ap,
+                      const SolveOutputs& out) {
+    DeviceGroup grp(devs, in.n1);
     const int P = grp.size();
     std::vector<std::unique_ptr<AlsSession>> ss;
     for (int p = 0; p < P; ++p) {
-        const auto [i0, i1] = grp.rows(p, n1);
+        const auto [i0, i1] = grp.rows(p, in.n1);
         TRITD_HIP(hipSetDevice(devs[p]));
-        ss.emplace_back(new AlsSession(devs[p], X + i0, n1, n1, n2, n3, i0, i1, r, maxIter, tol, A0,
-                                       B0, C0, nullptr, 0, grp.vst, /*defer_norm=*/true,
-                                       obs_rows(observed, i0), ho_rows(ho, i0),
-                                       ho ? ncvx : nullptr));
-        if (ncvx && !ho) ss.back()->enable_ncvx(*ncvx);
+        ss.push_back(make_als(devs[p], in.shard(i0, i1), ap, nullptr, grp.vst, /*defer_norm=*/true));
     }
     auto each = [&](auto&& f) { DeviceGroup::each(ss, f); };
     grp.reduce(ss, &AlsSession::red0, ss[0]->norm_count());
     each([](AlsSession& s) { s.set_norm_from_red0(); });
-    for (int it = 0; it < maxIter; ++it) {
+    for (int it = 0; it < ap.maxIter; ++it) {
         int k = 0;
         each([&](AlsSession& s) { k = s.next_iter(); });
         if (!k) break;
@@ -706,27 +741,52 @@ void run_als_group_serial(const std::vector<int>& devs, const double* X, int64_t
         grp.reduce(ss, &AlsSession::red0, ss[0]->fit_count());
         each([&](AlsSession& s) { s.phaseErr(k); });
         TRITD_HIP(hipSetDevice(devs[0]));
-        if (!ncvx) ss[0]->maybe_print(k);
+        if (!ap.ncvx) ss[0]->maybe_print(k);
         each([&](AlsSession& s) { s.phaseA(k); });
         grp.reduce(ss, &AlsSession::red1, ss[0]->red1_count());
         each([&](AlsSession& s) { s.phaseB(k); });
         grp.reduce(ss, &AlsSession::red2, ss[0]->red2_count());
         each([&](AlsSession& s) { s.phaseC(k); });
         each([&](AlsSession& s) { s.phaseEnd(k); });  // ncvx: errHist / stop after the updates
-        if (ncvx) {
+        if (ap.ncvx) {
             TRITD_HIP(hipSetDevice(devs[0]));
             ss[0]->maybe_print(k);
         }
     }
-    int k = 0;
     for (int p = 0; p < P; ++p) {
         TRITD_HIP(hipSetDevice(devs[p]));
-        ss[p]->get(A, p == 0 ? B : nullptr, p == 0 ? C : nullptr, p == 0 ? errHist : nullptr, &k);
-        if (ncvx && O) ss[p]->get_O(O + ss[p]->geom().i0, n1);
-        if (ho) get_holdout(*ss[p], p, *ho);
-        g_last_flags |= ss[p]->flags();
+        g_last_flags |= read_back(*ss[p], p, in, out);
     }
-    if (iters) *iters = k;
+}
+
+// triple_decomp_ALS / the test.m solver, the body of every tritd_als_* and
+// tritd_ncvx_* one-shot call.  On a device set: one AlsSession per shard with
+// a communicator (its run() carries the fit-sum, [M2 | A^TA] and M3
+// all-reduces), one host thread per shard (run_threaded).
+void solve_als(const Target& t, const ShardInputs& in, const AlsParams& ap,
+               const SolveOutputs& out) {
+    if (t.as_set && phase_serial()) return als_phase_serial(t.devs, in, ap, out);
+    if (t.devs.size() == 1) {
+        const auto s = make_als(t.devs[0], in, ap);
+        s->run(ap.maxIter);
+        g_last_flags |= read_back(*s, 0, in, out);
+        return;
+    }
+    DeviceGroup grp(t.devs, in.n1);
+    run_threaded(grp, [&](int p, tritd_comm* comm) {
+        const auto [i0, i1] = grp.rows(p, in.n1);
+        const auto s = make_als(t.devs[p], in.shard(i0, i1), ap, comm);
+        s->run(ap.maxIter);
+        return read_back(*s, p, in, out);
+    });
+}
+
+// A one-shot call: one at a time (g_mutex), its flags word started afresh
+template <class F>
+tritd_status one_shot(F&& f) {
+    std::lock_guard<std::mutex> lk(g_mutex);
+    g_last_flags = 0;
+    return guarded(f);
 }
 // fspecial('gaussian', 11, 1.5), then ssim_index's window/sum(sum(window));
 // column-major (the window is symmetric)
@@ -806,28 +866,11 @@ tritd_status tritd_admm_masked_f64(const double* D, const uint8_t* observed, int
                                    const double* B0, const double* C0, double* A, double* B,
                                    double* C, double* O, double* E, double* errHist, int32_t* iters,
                                    int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
+    return one_shot([&] {
+        const ShardInputs in = whole(D, n1, n2, n3, r, A0, B0, C0, observed);
         check_opts(opts);
-        check_dims(n1, n2, n3, r, true);  // fp64 ADMM: r <= 16 (r > 8 untuned)
-        need(D, "D"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        const tritd_opts o = normalized(opts);
-        if (device < 0 && g_devices.size() > 1) {
-            run_group(g_devices, D, sizeof(double), 0, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
-                      errHist, iters, observed);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, 0, nullptr, false,
-                  observed);
-        OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * sizeof(double));
-        s.run(o.maxIter);
-        pf.join();
-        int k = 0;
-        s.get(A, B, C, O, E, n1, errHist, &k, true);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "D", true, false);  // fp64 ADMM: r <= 16 (r > 8 untuned)
+        solve_admm(one_shot_target(device), in, normalized(opts), {A, B, C, O, E, errHist, iters});
     });
 }
 
@@ -839,32 +882,17 @@ tritd_status tritd_admm_holdout_f64(const double* D, const uint8_t* observed, co
                                     int32_t* iters, double* A_best, double* B_best, double* C_best,
                                     double* valHist, double* valHist1, int32_t* best_iter,
                                     int32_t* stop_reason, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
+    return one_shot([&] {
+        const ShardInputs in =
+            whole(D, n1, n2, n3, r, A0, B0, C0, observed, {holdout, patience, val_norm});
+        const HoldoutOutputs ho{A_best, B_best, C_best, valHist, valHist1, best_iter, stop_reason};
         check_opts(opts);
-        check_dims(n1, n2, n3, r, true);
-        need(D, "D"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        check_holdout(opts, patience, val_norm);
-        const tritd_opts o = normalized(opts);
-        const HoldoutArgs ho{{holdout, patience, val_norm}, A_best, B_best, C_best, valHist,
-                             valHist1, best_iter, stop_reason};
-        if (device < 0 && g_devices.size() > 1) {
-            run_group(g_devices, D, sizeof(double), 0, n1, n2, n3, r, o, A0, B0, C0, A, B, C, O, E,
-                      errHist, iters, observed, &ho);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, 0, nullptr, false,
-                  observed, ho.spec);
-        OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * sizeof(double));
-        s.run(o.maxIter);
-        pf.join();
-        int k = 0;
-        s.get(A, B, C, O, E, n1, errHist, &k, true);
-        get_holdout(s, 0, ho);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "D", true, true);
+        rule_patience(patience);
+        rule_val_norm(val_norm);
+        rule_holdout_model(opts);
+        solve_admm(one_shot_target(device), in, normalized(opts),
+                   {A, B, C, O, E, errHist, iters, &ho});
     });
 }
 
@@ -872,28 +900,46 @@ tritd_status tritd_admm_f32(const float* D, int64_t n1, int64_t n2, int64_t n3, 
                             const tritd_opts* opts, const double* A0, const double* B0,
                             const double* C0, double* A, double* B, double* C, float* O, float* E,
                             double* errHist, int32_t* iters, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
+    return one_shot([&] {
+        const ShardInputs in = whole(D, n1, n2, n3, r, A0, B0, C0, nullptr, {}, TRITD_SESSION_F32);
         check_opts(opts);
-        check_dims(n1, n2, n3, r, true);
-        need(D, "D"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        const tritd_opts o = normalized(opts);
-        if (device < 0 && g_devices.size() > 1) {
-            run_group(g_devices, D, sizeof(float), TRITD_SESSION_F32, n1, n2, n3, r, o, A0, B0, C0,
-                      A, B, C, O, E, errHist, iters);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        Session s(dev, D, n1, n1, n2, n3, 0, n1, r, o, A0, B0, C0, nullptr, TRITD_SESSION_F32);
-        OutputPrefault pf(O, E, (size_t)(n1 * n2 * n3) * sizeof(float));
-        s.run(o.maxIter);
-        pf.join();
-        int k = 0;
-        s.get(A, B, C, O, E, n1, errHist, &k, true);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "D", true, false);
+        solve_admm(one_shot_target(device), in, normalized(opts), {A, B, C, O, E, errHist, iters});
     });
+}
+
+tritd_status tritd_admm_sharded_virtual_f64(const double* D, int64_t n1, int64_t n2, int64_t n3,
+                                            int32_t r, const tritd_opts* opts, const double* A0,
+                                            const double* B0, const double* C0, int32_t nshards,
+                                            double* A, double* B, double* C, double* O, double* E,
+                                            double* errHist, int32_t* iters, int32_t device) {
+    return one_shot([&] {
+        const ShardInputs in = whole(D, n1, n2, n3, r, A0, B0, C0);
+        check_opts(opts);
+        check_inputs(in, "D", true, false);
+        solve_admm(virtual_target(nshards, n1, device), in, normalized(opts),
+                   {A, B, C, O, E, errHist, iters});
+    });
+}
+
+// the checks and the construction shared by the three session creators;
+// holdout: the creator takes a holdout mask (in.ho)
+static void session_create(tritd_session** out, int32_t device, const ShardInputs& in,
+                           const tritd_opts* opts, tritd_comm* comm, bool holdout) {
+    need(out, "out");
+    *out = nullptr;
+    check_opts(opts);
+    check_inputs(in, "D", true, holdout);  // ADMM, fp64 or fp32: r <= 16
+    check_shard(in, "ldD");
+    // (before any device is touched: a host without a GPU reports these too)
+    if (holdout || in.observed) rule_mask_f64(in.flags, holdout ? "holdout" : "observed");
+    if (holdout) {
+        rule_patience(in.ho.patience);
+        rule_val_norm(in.ho.val_norm);
+        rule_holdout_model(opts);
+    }
+    const int dev = pick_device(device);
+    *out = reinterpret_cast<tritd_session*>(new Session(dev, in, normalized(opts), comm));
 }
 
 tritd_status tritd_session_create(tritd_session** out, int32_t device, const void* D, int64_t ldD,
@@ -902,17 +948,8 @@ tritd_status tritd_session_create(tritd_session** out, int32_t device, const voi
                                   const double* B0, const double* C0, tritd_comm* comm,
                                   uint32_t flags) {
     return guarded([&] {
-        need(out, "out");
-        *out = nullptr;
-        check_opts(opts);
-        check_dims(n1, n2, n3, r, true);  // ADMM, fp64 or fp32: r <= 16
-        need(D, "D"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
-        if (ldD < i1 - i0) throw Error(TRITD_ERR_ARG, "ldD smaller than the shard");
-        const int dev = pick_device(device);
-        auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
-                              comm, flags);
-        *out = reinterpret_cast<tritd_session*>(s);
+        session_create(out, device, {D, ldD, n1, n2, n3, i0, i1, r, A0, B0, C0, nullptr, {}, flags},
+                       opts, comm, false);
     });
 }
 
@@ -922,20 +959,9 @@ tritd_status tritd_session_create_masked(tritd_session** out, int32_t device, co
                                          const tritd_opts* opts, const double* A0, const double* B0,
                                          const double* C0, tritd_comm* comm, uint32_t flags) {
     return guarded([&] {
-        need(out, "out");
-        *out = nullptr;
-        check_opts(opts);
-        check_dims(n1, n2, n3, r, true);
-        need(D, "D"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
-        if (ldD < i1 - i0) throw Error(TRITD_ERR_ARG, "ldD smaller than the shard");
-        // (before any device is touched: a host without a GPU reports it too)
-        if (observed && (flags & TRITD_SESSION_F32))
-            throw Error(TRITD_ERR_UNSUPPORTED, "observed (a mask) is implemented for a double D only");
-        const int dev = pick_device(device);
-        auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
-                              comm, flags, nullptr, false, observed);
-        *out = reinterpret_cast<tritd_session*>(s);
+        session_create(out, device,
+                       {D, ldD, n1, n2, n3, i0, i1, r, A0, B0, C0, observed, {}, flags}, opts, comm,
+                       false);
     });
 }
 
@@ -947,28 +973,15 @@ tritd_status tritd_session_create_holdout(tritd_session** out, int32_t device, c
                                           const double* B0, const double* C0, tritd_comm* comm,
                                           uint32_t flags) {
     return guarded([&] {
-        need(out, "out");
-        *out = nullptr;
-        check_opts(opts);
-        check_dims(n1, n2, n3, r, true);
-        need(D, "D"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
-        if (ldD < i1 - i0) throw Error(TRITD_ERR_ARG, "ldD smaller than the shard");
-        // (before any device is touched: a host without a GPU reports these too)
-        if (flags & TRITD_SESSION_F32)
-            throw Error(TRITD_ERR_UNSUPPORTED, "holdout (a mask) is implemented for a double D only");
-        check_holdout(opts, patience, val_norm);
-        const int dev = pick_device(device);
-        auto* s = new Session(dev, D, ldD, n1, n2, n3, i0, i1, r, normalized(opts), A0, B0, C0,
-                              comm, flags, nullptr, false, observed,
-                              HoldoutSpec{holdout, patience, val_norm});
-        *out = reinterpret_cast<tritd_session*>(s);
+        session_create(out, device,
+                       {D, ldD, n1, n2, n3, i0, i1, r, A0, B0, C0, observed,
+                        {holdout, patience, val_norm}, flags},
+                       opts, comm, true);
     });
 }
 
 static Session* holdout_session(tritd_session* s, const char* what) {
-    need(s, "session");
-    auto* S = reinterpret_cast<Session*>(s);
+    Session* S = admm(s);
     if (!S->holdout()) throw Error(TRITD_ERR_STATE, std::string(what) + ": not a holdout session");
     return S;
 }
@@ -983,8 +996,8 @@ tritd_status tritd_session_get_val(tritd_session* s, double* valHist, double* va
     return guarded([&] {
         int bi = 0, sr = 0;
         holdout_session(s, "get_val")->get_val(valHist, valHist1, &bi, &sr);
-        if (best_iter) *best_iter = bi;
-        if (stop_reason) *stop_reason = sr;
+        put(best_iter, bi);
+        put(stop_reason, sr);
     });
 }
 
@@ -1001,132 +1014,113 @@ tritd_status tritd_session_holdout_ms(tritd_session* s, double* score_ms, double
 }
 
 tritd_status tritd_session_mask_info(tritd_session* s, int32_t* masked, int64_t* observed_count) {
-    return guarded([&] {
-        need(s, "session");
-        int m = 0;
-        int64_t c = 0;
-        reinterpret_cast<Session*>(s)->mask_info(&m, &c);
-        if (masked) *masked = m;
-        if (observed_count) *observed_count = c;
-    });
+    return guarded([&] { admm(s)->mask_info(masked, observed_count); });
 }
 
 tritd_status tritd_session_run(tritd_session* s, int32_t iters) {
-    return guarded([&] {
-        need(s, "session");
-        reinterpret_cast<Session*>(s)->run(iters);
-    });
+    return guarded([&] { admm(s)->run(iters); });
 }
 
 tritd_status tritd_session_sync(tritd_session* s, int32_t* iters_done, int32_t* stopped) {
     return guarded([&] {
-        need(s, "session");
         int d = 0, st = 0;
-        reinterpret_cast<Session*>(s)->sync(&d, &st);
-        if (iters_done) *iters_done = d;
-        if (stopped) *stopped = st;
+        admm(s)->sync(&d, &st);
+        put(iters_done, d);
+        put(stopped, st);
     });
+}
+
+// O, E: double for an fp64 session (f32 = false), float for an fp32 one
+static void session_get(tritd_session* s, bool f32, double* A, double* B, double* C, void* O,
+                        void* E, int64_t ldOE, double* errHist, int32_t* iters) {
+    Session* S = admm(s);
+    if (S->is_f32() != f32)
+        throw Error(TRITD_ERR_ARG, f32 ? "fp64 session: use tritd_session_get"
+                                       : "fp32 session: use tritd_session_get_f32");
+    if ((O || E) && ldOE < S->geom().n1l) throw Error(TRITD_ERR_ARG, "ldOE smaller than the shard");
+    int k = 0;
+    S->get(A, B, C, O, E, ldOE, errHist, &k);
+    put(iters, k);
 }
 
 tritd_status tritd_session_get(tritd_session* s, double* A, double* B, double* C, double* O,
                                double* E, int64_t ldOE, double* errHist, int32_t* iters) {
-    return guarded([&] {
-        need(s, "session");
-        auto* S = reinterpret_cast<Session*>(s);
-        if (S->is_f32()) throw Error(TRITD_ERR_ARG, "fp32 session: use tritd_session_get_f32");
-        if ((O || E) && ldOE < S->geom().n1l) throw Error(TRITD_ERR_ARG, "ldOE smaller than the shard");
-        int k = 0;
-        S->get(A, B, C, O, E, ldOE, errHist, &k);
-        if (iters) *iters = k;
-    });
+    return guarded([&] { session_get(s, false, A, B, C, O, E, ldOE, errHist, iters); });
 }
 
 tritd_status tritd_session_get_f32(tritd_session* s, double* A, double* B, double* C, float* O,
                                    float* E, int64_t ldOE, double* errHist, int32_t* iters) {
-    return guarded([&] {
-        need(s, "session");
-        auto* S = reinterpret_cast<Session*>(s);
-        if (!S->is_f32()) throw Error(TRITD_ERR_ARG, "fp64 session: use tritd_session_get");
-        if ((O || E) && ldOE < S->geom().n1l) throw Error(TRITD_ERR_ARG, "ldOE smaller than the shard");
-        int k = 0;
-        S->get(A, B, C, O, E, ldOE, errHist, &k);
-        if (iters) *iters = k;
-    });
+    return guarded([&] { session_get(s, true, A, B, C, O, E, ldOE, errHist, iters); });
+}
+
+static void session_rre_parts(tritd_session* s, bool f32, const void* dX, int64_t ldX, double* num,
+                              double* den) {
+    Session* S = admm(s);
+    need(dX, "X"); need(num, "num"); need(den, "den");
+    if (S->is_f32() != f32)
+        throw Error(TRITD_ERR_ARG, f32 ? "fp64 session: use tritd_session_rre_parts"
+                                       : "fp32 session: use tritd_session_rre_parts_f32");
+    S->rre_parts(dX, ldX, num, den);
 }
 
 tritd_status tritd_session_rre_parts(tritd_session* s, const double* dX, int64_t ldX, double* num,
                                      double* den) {
-    return guarded([&] {
-        need(s, "session"); need(dX, "X"); need(num, "num"); need(den, "den");
-        auto* S = reinterpret_cast<Session*>(s);
-        if (S->is_f32()) throw Error(TRITD_ERR_ARG, "fp32 session: use tritd_session_rre_parts_f32");
-        S->rre_parts(dX, ldX, num, den);
-    });
+    return guarded([&] { session_rre_parts(s, false, dX, ldX, num, den); });
 }
 
 tritd_status tritd_session_rre_parts_f32(tritd_session* s, const float* dX, int64_t ldX,
                                          double* num, double* den) {
-    return guarded([&] {
-        need(s, "session"); need(dX, "X"); need(num, "num"); need(den, "den");
-        auto* S = reinterpret_cast<Session*>(s);
-        if (!S->is_f32()) throw Error(TRITD_ERR_ARG, "fp64 session: use tritd_session_rre_parts");
-        S->rre_parts(dX, ldX, num, den);
-    });
+    return guarded([&] { session_rre_parts(s, true, dX, ldX, num, den); });
 }
 
 tritd_status tritd_session_set_timing(tritd_session* s, int32_t enable) {
     return guarded([&] {
-        need(s, "session");
+        Session* S = admm(s);
         if (enable < 0 || enable > TRITD_TIMING_K5) throw Error(TRITD_ERR_ARG, "timing level 0..2");
-        reinterpret_cast<Session*>(s)->set_timing(enable);
+        S->set_timing(enable);
     });
 }
 
 tritd_status tritd_session_kernel_ms(tritd_session* s, double* fused_update_ms, double* mode3_ms,
                                      double* iteration_ms, int32_t* samples) {
     return guarded([&] {
-        need(s, "session");
         int n = 0;
-        reinterpret_cast<Session*>(s)->kernel_ms(fused_update_ms, mode3_ms, iteration_ms, &n);
-        if (samples) *samples = n;
+        admm(s)->kernel_ms(fused_update_ms, mode3_ms, iteration_ms, &n);
+        put(samples, n);
     });
 }
 
 tritd_status tritd_session_comm_ms(tritd_session* s, double* allreduce_ms, int32_t* per_iteration) {
     return guarded([&] {
-        need(s, "session");
         int n = 0;
-        reinterpret_cast<Session*>(s)->comm_ms(allreduce_ms, &n);
-        if (per_iteration) *per_iteration = n;
+        admm(s)->comm_ms(allreduce_ms, &n);
+        put(per_iteration, n);
     });
 }
 
 tritd_status tritd_session_probe(tritd_session* s, double* ms, int32_t cap, int32_t* n,
                                  int32_t* picked) {
     return guarded([&] {
-        need(s, "session");
-        const Session* q = reinterpret_cast<Session*>(s);
+        const Session* q = admm(s);
         const std::vector<double>& v = q->probe_ms();
         for (int32_t c = 0; ms && c < cap && c < (int32_t)v.size(); ++c) ms[c] = v[c];
-        if (n) *n = (int32_t)v.size();
-        if (picked) *picked = q->probe_pick();
+        put(n, v.size());
+        put(picked, q->probe_pick());
     });
 }
 
 tritd_status tritd_session_counters(tritd_session* s, int64_t* dense_tiles_total,
                                     int64_t* tiles_per_launch) {
-    return guarded([&] {
-        need(s, "session");
-        reinterpret_cast<Session*>(s)->counters(dense_tiles_total, tiles_per_launch);
-    });
+    return guarded([&] { admm(s)->counters(dense_tiles_total, tiles_per_launch); });
 }
 
 tritd_status tritd_session_k5_profile(tritd_session* s, int32_t* dense_streams,
                                       int32_t* slot_accesses) {
     return guarded([&] {
-        need(s, "session"); need(dense_streams, "dense_streams"); need(slot_accesses, "slot_accesses");
+        Session* S = admm(s);
+        need(dense_streams, "dense_streams"); need(slot_accesses, "slot_accesses");
         int a = 0, b = 0;
-        reinterpret_cast<Session*>(s)->k5_profile(&a, &b);
+        S->k5_profile(&a, &b);
         *dense_streams = a;
         *slot_accesses = b;
     });
@@ -1134,9 +1128,9 @@ tritd_status tritd_session_k5_profile(tritd_session* s, int32_t* dense_streams,
 
 tritd_status tritd_session_flags(tritd_session* s, uint32_t* flags) {
     return guarded([&] {
-        need(s, "session");
+        Session* S = admm(s);
         need(flags, "flags");
-        *flags = reinterpret_cast<Session*>(s)->flags();
+        *flags = S->flags();
     });
 }
 
@@ -1209,23 +1203,6 @@ tritd_status tritd_comm_info(tritd_comm* c, int32_t* nranks, int32_t* rank, int3
     });
 }
 
-tritd_status tritd_admm_sharded_virtual_f64(const double* D, int64_t n1, int64_t n2, int64_t n3,
-                                            int32_t r, const tritd_opts* opts, const double* A0,
-                                            const double* B0, const double* C0, int32_t nshards,
-                                            double* A, double* B, double* C, double* O, double* E,
-                                            double* errHist, int32_t* iters, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
-        check_opts(opts);
-        check_dims(n1, n2, n3, r, true);  // fp64 ADMM: r <= 16 (r > 8 untuned)
-        need(D, "D"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (nshards < 1 || nshards > 16 || nshards > n1) throw Error(TRITD_ERR_ARG, "nshards must be in 1..min(16,n1)");
-        const int dev = pick_device(device);
-        run_group(std::vector<int>(nshards, dev), D, sizeof(double), 0, n1, n2, n3, r,
-                  normalized(opts), A0, B0, C0, A, B, C, O, E, errHist, iters);
-    });
-}
 
 tritd_status tritd_set_devices(const int32_t* devices, int32_t n) {
     std::lock_guard<std::mutex> lk(g_mutex);
@@ -1264,26 +1241,12 @@ tritd_status tritd_als_masked_f64(const double* X, const uint8_t* observed, int6
                                   int64_t n3, int32_t r, const tritd_opts* opts, const double* A0,
                                   const double* B0, const double* C0, double* A, double* B,
                                   double* C, double* errHist, int32_t* iters, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
+    return one_shot([&] {
+        const ShardInputs in = whole(X, n1, n2, n3, r, A0, B0, C0, observed);
         check_als_opts(opts);
-        check_dims(n1, n2, n3, r);
-        need(X, "X"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        const int maxIter = opts->maxIter < 0 ? 0 : opts->maxIter;
-        if (device < 0 && g_devices.size() > 1) {
-            run_als_group(g_devices, X, n1, n2, n3, r, maxIter, opts->tol, A0, B0, C0, A, B, C,
-                          errHist, iters, nullptr, nullptr, observed);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, maxIter, opts->tol, A0, B0, C0, nullptr, 0,
-                     nullptr, false, observed);
-        s.run(maxIter);
-        int k = 0;
-        s.get(A, B, C, errHist, &k);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "X", false, false);
+        solve_als(one_shot_target(device), in, als_params(opts),
+                  {A, B, C, nullptr, nullptr, errHist, iters});
     });
 }
 
@@ -1294,30 +1257,14 @@ tritd_status tritd_als_holdout_f64(const double* X, const uint8_t* observed, con
                                    double* C, double* errHist, int32_t* iters, double* A_best,
                                    double* B_best, double* C_best, double* valHist,
                                    int32_t* best_iter, int32_t* stop_reason, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
+    return one_shot([&] {
+        const ShardInputs in = whole(X, n1, n2, n3, r, A0, B0, C0, observed, {holdout, patience, 2});
+        const HoldoutOutputs ho{A_best, B_best, C_best, valHist, nullptr, best_iter, stop_reason};
         check_als_opts(opts);
-        check_dims(n1, n2, n3, r);
-        need(X, "X"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        const int maxIter = opts->maxIter < 0 ? 0 : opts->maxIter;
-        const HoldoutArgs ho{{holdout, patience, 2}, A_best, B_best, C_best, valHist, nullptr,
-                             best_iter, stop_reason};
-        if (device < 0 && g_devices.size() > 1) {
-            run_als_group(g_devices, X, n1, n2, n3, r, maxIter, opts->tol, A0, B0, C0, A, B, C,
-                          errHist, iters, nullptr, nullptr, observed, &ho);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, maxIter, opts->tol, A0, B0, C0, nullptr, 0,
-                     nullptr, false, observed, ho.spec);
-        s.run(maxIter);
-        int k = 0;
-        s.get(A, B, C, errHist, &k);
-        get_holdout(s, 0, ho);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "X", false, true);
+        rule_patience(patience);
+        solve_als(one_shot_target(device), in, als_params(opts),
+                  {A, B, C, nullptr, nullptr, errHist, iters, &ho});
     });
 }
 
@@ -1326,18 +1273,12 @@ tritd_status tritd_als_sharded_virtual_f64(const double* X, int64_t n1, int64_t 
                                            const double* B0, const double* C0, int32_t nshards,
                                            double* A, double* B, double* C, double* errHist,
                                            int32_t* iters, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
+    return one_shot([&] {
+        const ShardInputs in = whole(X, n1, n2, n3, r, A0, B0, C0);
         check_als_opts(opts);
-        check_dims(n1, n2, n3, r);
-        need(X, "X"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        if (nshards < 1 || nshards > 16 || nshards > n1)
-            throw Error(TRITD_ERR_ARG, "nshards must be in 1..min(16,n1)");
-        const int dev = pick_device(device);
-        run_als_group(std::vector<int>(nshards, dev), X, n1, n2, n3, r,
-                      opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0, A, B, C,
-                      errHist, iters);
+        check_inputs(in, "X", false, false);
+        solve_als(virtual_target(nshards, n1, device), in, als_params(opts),
+                  {A, B, C, nullptr, nullptr, errHist, iters});
     });
 }
 
@@ -1350,36 +1291,26 @@ tritd_status tritd_ncvx_f64(const double* X, int64_t n1, int64_t n2, int64_t n3,
                                  maxIter, tol, A0, B0, C0, A, B, C, O, errHist, iters, device);
 }
 
+// the outputs test.m always returns
+static void need_ncvx_outputs(const SolveOutputs& out) {
+    need(out.A, "A"); need(out.B, "B"); need(out.C, "C"); need(out.O, "O");
+    need(out.errHist, "errHist");
+}
+
 tritd_status tritd_ncvx_masked_f64(const double* X, const uint8_t* observed, int64_t n1, int64_t n2,
                                    int64_t n3, int32_t r, double rho, double lambda, double gamma_A,
                                    double epsilon, double p, double theta, int32_t maxIter,
                                    double tol, const double* A0, const double* B0, const double* C0,
                                    double* A, double* B, double* C, double* O, double* errHist,
                                    int32_t* iters, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
-        check_dims(n1, n2, n3, r);
-        need(X, "X"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        need(A, "A"); need(B, "B"); need(C, "C"); need(O, "O"); need(errHist, "errHist");
-        if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+    return one_shot([&] {
+        const ShardInputs in = whole(X, n1, n2, n3, r, A0, B0, C0, observed);
+        const SolveOutputs out{A, B, C, O, nullptr, errHist, iters};
         const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
-        const int mi = maxIter < 0 ? 0 : maxIter;
-        if (device < 0 && g_devices.size() > 1) {
-            run_als_group(g_devices, X, n1, n2, n3, r, mi, tol, A0, B0, C0, A, B, C, errHist, iters,
-                          &np, O, observed);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, mi, tol, A0, B0, C0, nullptr, 0, nullptr,
-                     false, observed);
-        s.enable_ncvx(np);
-        s.run(mi);
-        int k = 0;
-        s.get(A, B, C, errHist, &k);
-        s.get_O(O, n1);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "X", false, false);
+        need_ncvx_outputs(out);
+        np.check();
+        solve_als(one_shot_target(device), in, {maxIter < 0 ? 0 : maxIter, tol, &np}, out);
     });
 }
 
@@ -1392,35 +1323,37 @@ tritd_status tritd_ncvx_holdout_f64(const double* X, const uint8_t* observed, co
                                     double* errHist, int32_t* iters, double* A_best, double* B_best,
                                     double* C_best, double* valHist, double* valHist1,
                                     int32_t* best_iter, int32_t* stop_reason, int32_t device) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_last_flags = 0;
-    return guarded([&] {
-        check_dims(n1, n2, n3, r);
-        need(X, "X"); need(holdout, "holdout"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-        need(A, "A"); need(B, "B"); need(C, "C"); need(O, "O"); need(errHist, "errHist");
-        if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
-        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
+    return one_shot([&] {
+        const ShardInputs in =
+            whole(X, n1, n2, n3, r, A0, B0, C0, observed, {holdout, patience, val_norm});
+        const HoldoutOutputs ho{A_best, B_best, C_best, valHist, valHist1, best_iter, stop_reason};
+        const SolveOutputs out{A, B, C, O, nullptr, errHist, iters, &ho};
         const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
-        const int mi = maxIter < 0 ? 0 : maxIter;
-        const HoldoutArgs ho{{holdout, patience, val_norm}, A_best, B_best, C_best, valHist,
-                             valHist1, best_iter, stop_reason};
-        if (device < 0 && g_devices.size() > 1) {
-            run_als_group(g_devices, X, n1, n2, n3, r, mi, tol, A0, B0, C0, A, B, C, errHist, iters,
-                          &np, O, observed, &ho);
-            return;
-        }
-        const int dev = pick_device(device < 0 && !g_devices.empty() ? g_devices[0] : device);
-        AlsSession s(dev, X, n1, n1, n2, n3, 0, n1, r, mi, tol, A0, B0, C0, nullptr, 0, nullptr,
-                     false, observed, ho.spec, &np);
-        s.run(mi);
-        int k = 0;
-        s.get(A, B, C, errHist, &k);
-        s.get_O(O, n1);
-        get_holdout(s, 0, ho);
-        g_last_flags |= s.flags();
-        if (iters) *iters = k;
+        check_inputs(in, "X", false, true);
+        need_ncvx_outputs(out);
+        np.check();
+        rule_patience(patience);
+        rule_val_norm(val_norm);
+        solve_als(one_shot_target(device), in, {maxIter < 0 ? 0 : maxIter, tol, &np}, out);
     });
+}
+
+// the checks and the construction shared by the four session creators
+static void als_session_create(tritd_als_session** out, int32_t device, const ShardInputs& in,
+                               const tritd_opts* opts, tritd_comm* comm, int32_t quiet,
+                               const NcvxParams* ncvx = nullptr) {
+    need(out, "out");
+    *out = nullptr;
+    check_als_opts(opts);
+    check_inputs(in, "X", false, false);
+    if (in.flags & ~(uint32_t)TRITD_SESSION_D_ON_DEVICE)
+        throw Error(TRITD_ERR_UNSUPPORTED, "ALS sessions are fp64 (flags: D_ON_DEVICE only)");
+    check_shard(in, "ldX");
+    const int dev = pick_device(device);
+    const AlsParams ap = als_params(opts);
+    auto* s = new AlsSession(dev, in, ap.maxIter, ap.tol, ncvx, comm);
+    s->set_quiet(quiet != 0);
+    *out = reinterpret_cast<tritd_als_session*>(s);
 }
 
 tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, const double* X,
@@ -1432,30 +1365,6 @@ tritd_status tritd_als_session_create(tritd_als_session** out, int32_t device, c
                                            A0, B0, C0, comm, flags, quiet);
 }
 
-// the checks and the construction shared by the three session creators
-static void als_session_create(tritd_als_session** out, int32_t device, const double* X,
-                        const uint8_t* observed, const HoldoutSpec& ho, int64_t ldX, int64_t n1,
-                        int64_t n2, int64_t n3, int64_t i0, int64_t i1,
-                        int32_t r, const tritd_opts* opts, const double* A0, const double* B0,
-                        const double* C0, tritd_comm* comm, uint32_t flags, int32_t quiet,
-                        const NcvxParams* ncvx = nullptr) {
-    need(out, "out");
-    *out = nullptr;
-    check_als_opts(opts);
-    check_dims(n1, n2, n3, r);
-    need(X, "X"); need(A0, "A0"); need(B0, "B0"); need(C0, "C0");
-    if (flags & ~(uint32_t)TRITD_SESSION_D_ON_DEVICE)
-        throw Error(TRITD_ERR_UNSUPPORTED, "ALS sessions are fp64 (flags: D_ON_DEVICE only)");
-    if (i0 < 0 || i1 > n1 || i0 >= i1) throw Error(TRITD_ERR_ARG, "bad shard range");
-    if (ldX < i1 - i0) throw Error(TRITD_ERR_ARG, "ldX smaller than the shard");
-    const int dev = pick_device(device);
-    auto* s = new AlsSession(dev, X, ldX, n1, n2, n3, i0, i1, r,
-                             opts->maxIter < 0 ? 0 : opts->maxIter, opts->tol, A0, B0, C0, comm,
-                             flags, nullptr, false, observed, ho, ncvx);
-    s->set_quiet(quiet != 0);
-    *out = reinterpret_cast<tritd_als_session*>(s);
-}
-
 tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t device,
                                              const double* X, const uint8_t* observed, int64_t ldX,
                                              int64_t n1, int64_t n2, int64_t n3, int64_t i0,
@@ -1463,8 +1372,9 @@ tritd_status tritd_als_session_create_masked(tritd_als_session** out, int32_t de
                                              const double* A0, const double* B0, const double* C0,
                                              tritd_comm* comm, uint32_t flags, int32_t quiet) {
     return guarded([&] {
-        als_session_create(out, device, X, observed, {}, ldX, n1, n2, n3, i0, i1, r, opts, A0,
-                           B0, C0, comm, flags, quiet);
+        als_session_create(out, device,
+                           {X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, observed, {}, flags}, opts,
+                           comm, quiet);
     });
 }
 
@@ -1479,9 +1389,11 @@ tritd_status tritd_als_session_create_holdout(tritd_als_session** out, int32_t d
         need(out, "out");
         *out = nullptr;
         need(holdout, "holdout");
-        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        als_session_create(out, device, X, observed, {holdout, patience, 2}, ldX, n1, n2, n3, i0, i1,
-                           r, opts, A0, B0, C0, comm, flags, quiet);
+        rule_patience(patience);
+        als_session_create(out, device,
+                           {X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, observed,
+                            {holdout, patience, 2}, flags},
+                           opts, comm, quiet);
     });
 }
 
@@ -1495,35 +1407,37 @@ tritd_status tritd_als_session_create_ncvx_holdout(
         need(out, "out");
         *out = nullptr;
         need(holdout, "holdout");
-        if (patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        if (val_norm != 1 && val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
-        if (!(rho != 0.0)) throw Error(TRITD_ERR_ARG, "rho must be non-zero");
+        rule_patience(patience);
+        rule_val_norm(val_norm);
         const NcvxParams np{rho, lambda, gamma_A, epsilon, p, theta};
-        als_session_create(out, device, X, observed, {holdout, patience, val_norm}, ldX, n1, n2, n3,
-                           i0, i1, r, opts, A0, B0, C0, comm, flags, quiet, &np);
+        np.check();
+        als_session_create(out, device,
+                           {X, ldX, n1, n2, n3, i0, i1, r, A0, B0, C0, observed,
+                            {holdout, patience, val_norm}, flags},
+                           opts, comm, quiet, &np);
     });
+}
+
+static AlsSession* ncvx_holdout_session(tritd_als_session* s, const char* what) {
+    AlsSession* as = als(s);
+    if (!as->ncvx_holdout())
+        throw Error(TRITD_ERR_STATE, std::string(what) + ": not a nonconvex holdout session");
+    return as;
 }
 
 tritd_status tritd_als_session_get_val2(tritd_als_session* s, double* valHist, double* valHist1,
                                         int32_t* best_iter, int32_t* stop_reason) {
     return guarded([&] {
-        need(s, "session");
-        auto* as = reinterpret_cast<AlsSession*>(s);
-        if (!as->ncvx_holdout())
-            throw Error(TRITD_ERR_STATE, "get_val2: not a nonconvex holdout session");
         int bi = 0, sr = 0;
-        as->get_val(valHist, valHist1, &bi, &sr);
-        if (best_iter) *best_iter = bi;
-        if (stop_reason) *stop_reason = sr;
+        ncvx_holdout_session(s, "get_val2")->get_val(valHist, valHist1, &bi, &sr);
+        put(best_iter, bi);
+        put(stop_reason, sr);
     });
 }
 
 tritd_status tritd_als_session_holdout_ms(tritd_als_session* s, double* score_ms, double* tail_ms) {
     return guarded([&] {
-        need(s, "session");
-        auto* as = reinterpret_cast<AlsSession*>(s);
-        if (!as->ncvx_holdout())
-            throw Error(TRITD_ERR_STATE, "holdout_ms: not a nonconvex holdout session");
+        AlsSession* as = ncvx_holdout_session(s, "holdout_ms");
         as->sync(nullptr, nullptr);
         as->holdout_ms(score_ms, tail_ms);
     });
@@ -1531,8 +1445,7 @@ tritd_status tritd_als_session_holdout_ms(tritd_als_session* s, double* score_ms
 
 tritd_status tritd_als_session_holdout_info(tritd_als_session* s, int64_t* count, double* norm) {
     return guarded([&] {
-        need(s, "session");
-        auto* as = reinterpret_cast<AlsSession*>(s);
+        AlsSession* as = als(s);
         if (!as->holdout()) throw Error(TRITD_ERR_STATE, "holdout_info: not a holdout session");
         as->holdout_info(count, norm);
     });
@@ -1541,46 +1454,31 @@ tritd_status tritd_als_session_holdout_info(tritd_als_session* s, int64_t* count
 tritd_status tritd_als_session_get_val(tritd_als_session* s, double* valHist, int32_t* best_iter,
                                        int32_t* stop_reason) {
     return guarded([&] {
-        need(s, "session");
         int bi = 0, sr = 0;
-        reinterpret_cast<AlsSession*>(s)->get_val(valHist, nullptr, &bi, &sr);
-        if (best_iter) *best_iter = bi;
-        if (stop_reason) *stop_reason = sr;
+        als(s)->get_val(valHist, nullptr, &bi, &sr);
+        put(best_iter, bi);
+        put(stop_reason, sr);
     });
 }
 
 tritd_status tritd_als_session_get_best(tritd_als_session* s, double* A, double* B, double* C) {
-    return guarded([&] {
-        need(s, "session");
-        reinterpret_cast<AlsSession*>(s)->get_best(A, B, C);
-    });
+    return guarded([&] { als(s)->get_best(A, B, C); });
 }
 
 tritd_status tritd_als_session_mask_info(tritd_als_session* s, int32_t* masked,
                                          int64_t* observed_count) {
-    return guarded([&] {
-        need(s, "session");
-        int m = 0;
-        int64_t c = 0;
-        reinterpret_cast<AlsSession*>(s)->mask_info(&m, &c);
-        if (masked) *masked = m;
-        if (observed_count) *observed_count = c;
-    });
+    return guarded([&] { als(s)->mask_info(masked, observed_count); });
 }
 
 tritd_status tritd_als_session_set_ncvx(tritd_als_session* s, double rho, double lambda,
                                         double gamma_A, double epsilon, double p, double theta) {
-    return guarded([&] {
-        need(s, "session");
-        reinterpret_cast<AlsSession*>(s)->enable_ncvx(NcvxParams{rho, lambda, gamma_A, epsilon, p, theta});
-    });
+    return guarded([&] { als(s)->enable_ncvx(NcvxParams{rho, lambda, gamma_A, epsilon, p, theta}); });
 }
 
 tritd_status tritd_als_session_get_O(tritd_als_session* s, double* O, int64_t ldO) {
     return guarded([&] {
-        need(s, "session");
+        AlsSession* as = als(s);
         need(O, "O");
-        auto* as = reinterpret_cast<AlsSession*>(s);
         if (!as->ncvx()) throw Error(TRITD_ERR_STATE, "get_O: not a nonconvex (test.m) session");
         if (ldO < as->geom().n1l) throw Error(TRITD_ERR_ARG, "ldO smaller than the shard");
         as->get_O(O, ldO);
@@ -1588,54 +1486,45 @@ tritd_status tritd_als_session_get_O(tritd_als_session* s, double* O, int64_t ld
 }
 
 tritd_status tritd_als_session_run(tritd_als_session* s, int32_t iters) {
-    return guarded([&] {
-        need(s, "session");
-        reinterpret_cast<AlsSession*>(s)->run(iters);
-    });
+    return guarded([&] { als(s)->run(iters); });
 }
 
 tritd_status tritd_als_session_sync(tritd_als_session* s, int32_t* iters_done, int32_t* stopped) {
     return guarded([&] {
-        need(s, "session");
         int d = 0, st = 0;
-        reinterpret_cast<AlsSession*>(s)->sync(&d, &st);
-        if (iters_done) *iters_done = d;
-        if (stopped) *stopped = st;
+        als(s)->sync(&d, &st);
+        put(iters_done, d);
+        put(stopped, st);
     });
 }
 
 tritd_status tritd_als_session_get(tritd_als_session* s, double* A, double* B, double* C,
                                    double* errHist, int32_t* iters) {
     return guarded([&] {
-        need(s, "session");
         int k = 0;
-        reinterpret_cast<AlsSession*>(s)->get(A, B, C, errHist, &k);
-        if (iters) *iters = k;
+        als(s)->get(A, B, C, errHist, &k);
+        put(iters, k);
     });
 }
 
 tritd_status tritd_als_session_set_timing(tritd_als_session* s, int32_t enable) {
-    return guarded([&] {
-        need(s, "session");
-        reinterpret_cast<AlsSession*>(s)->set_timing(enable != 0);
-    });
+    return guarded([&] { als(s)->set_timing(enable != 0); });
 }
 
 tritd_status tritd_als_session_kernel_ms(tritd_als_session* s, double* fit_ms, double* mode3_ms,
                                          double* iteration_ms, int32_t* samples) {
     return guarded([&] {
-        need(s, "session");
         int n = 0;
-        reinterpret_cast<AlsSession*>(s)->kernel_ms(fit_ms, mode3_ms, iteration_ms, &n);
-        if (samples) *samples = n;
+        als(s)->kernel_ms(fit_ms, mode3_ms, iteration_ms, &n);
+        put(samples, n);
     });
 }
 
 tritd_status tritd_als_session_flags(tritd_als_session* s, uint32_t* flags) {
     return guarded([&] {
-        need(s, "session");
+        AlsSession* as = als(s);
         need(flags, "flags");
-        *flags = reinterpret_cast<AlsSession*>(s)->flags();
+        *flags = as->flags();
     });
 }
 

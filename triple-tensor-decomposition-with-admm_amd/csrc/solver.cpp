@@ -97,25 +97,19 @@ void download_factor(const Geom& g, const double* dev, size_t n,
 }
 
 // ---------------------------------------------------------------------------
-Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3,
-                 int64_t i0, int64_t i1, int r, const tritd_opts& o, const double* A0,
-                 const double* B0, const double* C0, tritd_comm* comm, uint32_t flags,
-                 hipStream_t shared_stream, bool defer_normD, const uint8_t* observed,
-                 const HoldoutSpec& ho)
+// (the argument rules — a mask needs a double D, no holdout with the Qi model,
+// patience, val_norm — are api.cpp's: every construction passes them first)
+Session::Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_comm* comm,
+                 hipStream_t shared_stream, bool defer_normD)
     : device_(device), o_(o), comm_(comm) {
-    const uint8_t* holdout = ho.mask;
+    const void* D = in.D;
+    const int64_t ldD = in.ld, n2 = in.n2, n3 = in.n3;
+    const uint32_t flags = in.flags;
+    const uint8_t *observed = in.observed, *holdout = in.ho.mask;
     TRITD_HIP(hipSetDevice(device_));
-    g_ = make_geom(n1, n2, n3, i0, i1, r);
+    g_ = make_geom(in.n1, n2, n3, in.i0, in.i1, in.r);
     f32_ = (flags & TRITD_SESSION_F32) != 0;
-    if ((observed || holdout) && f32_)
-        throw Error(TRITD_ERR_UNSUPPORTED, "observed (a mask) is implemented for a double D only");
-    if (holdout) {
-        if (o_.model == TRITD_MODEL_QI)  // (the Qi K5 launch carries its own fused finish)
-            throw Error(TRITD_ERR_UNSUPPORTED, "holdout is not implemented for opts.model='qi'");
-        if (ho.patience < 0) throw Error(TRITD_ERR_ARG, "patience must be >= 0");
-        if (ho.val_norm != 1 && ho.val_norm != 2) throw Error(TRITD_ERR_ARG, "val_norm must be 1 or 2");
-        holdout_ = true;
-    }
+    holdout_ = holdout != nullptr;
     probe_ = (flags & TRITD_SESSION_PROBE) != 0;
     es_ = f32_ ? sizeof(float) : sizeof(double);
     // fp32 path and fp64 r = 9..16: padded ranks 16/32/48/64/128/256 (the
@@ -271,7 +265,7 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
     TRITD_HIP(hipMemsetAsync(ctrl_, 0, ctrl_bytes, st_));
     if (holdout_) {
         hset_.alloc(g_);
-        val_.alloc(mi, /*l1=*/true, AhB_[0].n, Bh_.n, Ch_.n, ho, st_);
+        val_.alloc(mi, /*l1=*/true, AhB_[0].n, Bh_.n, Ch_.n, in.ho, st_);
     }
 
     // D -> tile-major device layout (one-off)
@@ -296,7 +290,7 @@ Session::Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2,
         if (observed || holdout)
             pack_mask(observed, ldD, (flags & TRITD_SESSION_D_ON_DEVICE) != 0, holdout);
     }
-    upload_factors(A0, B0, C0);
+    upload_factors(in.A0, in.B0, in.C0);
     if (holdout_) val_.seed(Ah_.p, Bh_.p, Ch_.p);
 
     // normD = norm(D(:))  (:28)

@@ -67,14 +67,38 @@ void unpack_C(const Geom& g, const std::vector<double>& Ch, double* C);
 void download_factor(const Geom& g, const double* dev, size_t n,
                      void (*unpack)(const Geom&, const std::vector<double>&, double*), double* out);
 
+// What a session is made from: the data of a whole tensor (i0 = 0, i1 = n1) or
+// of one mode-1 shard [i0, i1), the initial factors, the masks and the
+// TRITD_SESSION_* flags.  D points at row i0; with TRITD_SESSION_D_ON_DEVICE
+// it and the masks are device addresses.
+struct ShardInputs {
+    const void* D = nullptr;  // double, or float with TRITD_SESSION_F32
+    int64_t ld = 0;           // elements between the fibres of D (and of the masks)
+    int64_t n1 = 0, n2 = 0, n3 = 0, i0 = 0, i1 = 0;
+    int r = 0;
+    const double *A0 = nullptr, *B0 = nullptr, *C0 = nullptr;
+    const uint8_t* observed = nullptr;  // a byte mask laid out like D, TRITD_OBSERVED_NAN or null
+    HoldoutSpec ho;
+    uint32_t flags = 0;
+    size_t es() const { return (flags & TRITD_SESSION_F32) ? sizeof(float) : sizeof(double); }
+    // the view of rows [a, b) of a whole-tensor description
+    ShardInputs shard(int64_t a, int64_t b) const {
+        ShardInputs s = *this;
+        s.D = static_cast<const char*>(D) + a * es();
+        s.i0 = a;
+        s.i1 = b;
+        s.observed = obs_rows(observed, a);
+        s.ho = ho.rows(a);
+        return s;
+    }
+};
+
 class Session {
    public:
-    // D: double, or float when flags has TRITD_SESSION_F32 (the fp32 data path)
-    Session(int device, const void* D, int64_t ldD, int64_t n1, int64_t n2, int64_t n3, int64_t i0,
-            int64_t i1, int r, const tritd_opts& o, const double* A0, const double* B0,
-            const double* C0, tritd_comm* comm, uint32_t flags, hipStream_t shared_stream = nullptr,
-            bool defer_normD = false, const uint8_t* observed = nullptr,
-            const HoldoutSpec& ho = {});
+    // shared_stream, defer_normD: a device group driven phase by phase from one
+    // host thread (api.cpp) shares a stream and reduces normD itself
+    Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_comm* comm = nullptr,
+            hipStream_t shared_stream = nullptr, bool defer_normD = false);
     ~Session();
 
     // Enqueue iterations (full collective schedule; used without a virtual group)

@@ -162,6 +162,96 @@ def initial_factors(n1, n2, n3, r, opts=None, rng=None):
     return A0, B0, C0
 
 
+class _OneShot:
+    """One one-shot solve as the four public functions make it: the normalised
+    initial factors, the output arrays (factors, ``tensors`` of the data's
+    type, errHist, k, and the holdout outputs when ``hold`` is given; ``l1``:
+    valHist1 too), the C call and the returned tuple."""
+
+    def __init__(self, X, r, maxIter, opts, A0, B0, C0, *, tensors, obs=None, hold=None, l1=True):
+        self.X, self.obs, self.hold = X, obs, hold
+        n1, n2, n3 = _size3(X)
+        self.dims = (n1, n2, n3, int(r))
+        if A0 is None or B0 is None or C0 is None:
+            self.start = initial_factors(*self.dims, opts)
+        else:
+            self.start = initial_factors(*self.dims, dict(A0=A0, B0=B0, C0=C0))
+        self.factors = [np.zeros(a.shape, order="F") for a in self.start]
+        # (a tensor the caller does not want back is not allocated: null to the library)
+        self.tensors = [np.zeros((n1, n2, n3), order="F", dtype=X.dtype) if want else None
+                        for want in tensors]
+        hist = max(maxIter, 1)
+        self.errHist, self.k = np.zeros(hist), _lib.i32(0)
+        if hold is not None:
+            self.best = [np.zeros_like(a) for a in self.factors]
+            self.val = [np.zeros(hist) for _ in range(2 if l1 else 1)]
+            self.best_iter, self.why = _lib.i32(0), _lib.i32(0)
+
+    def solve(self, symbols, what, params, device, holdout_params=(), virtual_shards=0, form=None):
+        """Call ``symbols[form]``; the form follows from the arguments unless given."""
+        if form is None:
+            form = ("holdout" if self.hold is not None else
+                    "virtual" if virtual_shards and virtual_shards > 1 else
+                    "masked" if self.obs is not None else "plain")
+        holdout = form == "holdout"
+        args = [_ptr(self.X)]
+        if holdout or form == "masked":
+            args.append(_ptr(self.obs))
+        if holdout:
+            args.append(_ptr(self.hold))
+        args += [*self.dims, *params]
+        if holdout:
+            args += holdout_params
+        args += [_ptr(a) for a in self.start]
+        if form == "virtual":
+            args.append(int(virtual_shards))
+        args += [_ptr(a) for a in (*self.factors, *self.tensors, self.errHist)]
+        args.append(C.byref(self.k))
+        if holdout:
+            args += [_ptr(a) for a in (*self.best, *self.val)]
+            args += [C.byref(self.best_iter), C.byref(self.why)]
+        check_flags(getattr(lib, symbols[form])(*args, int(device)), what)
+
+    def result(self, leading, trailing=()):
+        """(A, B, C, *leading, errHist(1:k), *trailing[, the holdout dict]);
+        a ``_K`` in ``trailing`` stands for the iteration count."""
+        k = self.k.value
+        out = [*self.factors, *leading, self.errHist[:k].copy()]
+        out += [k if t is _K else t for t in trailing]
+        if self.hold is not None:
+            d = dict(zip(("valHist", "valHist1"), (v[:k].copy() for v in self.val)))
+            d.update(best_iter=self.best_iter.value, stop_reason=self.why.value,
+                     A_best=self.best[0], B_best=self.best[1], C_best=self.best[2],
+                     holdout_count=_holdout_count(self.hold, self.obs, self.X))
+            out.append(d)
+        return tuple(out)
+
+
+_K = object()  # _OneShot.result: the iteration count goes here
+
+_ADMM = dict(plain="tritd_admm_f64", masked="tritd_admm_masked_f64",
+             holdout="tritd_admm_holdout_f64", virtual="tritd_admm_sharded_virtual_f64",
+             f32="tritd_admm_f32")
+_ALS = dict(plain="tritd_als_f64", masked="tritd_als_masked_f64", holdout="tritd_als_holdout_f64",
+            virtual="tritd_als_sharded_virtual_f64")
+_NCVX = dict(plain="tritd_ncvx_f64", masked="tritd_ncvx_masked_f64",
+             holdout="tritd_ncvx_holdout_f64")
+
+
+def _masks(observed, holdout, X, what, virtual_shards=0):
+    """observed=, holdout= of a one-shot call -> (obs, hold) byte arrays (or None, _NAN)"""
+    obs = hold = None
+    if observed is not None:
+        obs = _observed_bytes(observed, X.shape, what)
+        if virtual_shards and virtual_shards > 1:
+            raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
+    if holdout is not None:
+        hold = _observed_bytes(holdout, X.shape, what, "holdout")
+        if virtual_shards and virtual_shards > 1:
+            raise ValueError("holdout with virtual_shards: use set_devices([d] * P) and device=-1")
+    return obs, hold
+
+
 def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, return_E=False,
                        return_iters=False, virtual_shards=0, observed=None, holdout=None,
                        patience=0, val_norm=2):
@@ -200,104 +290,19 @@ def triple_decomp_ADMM(D, r, opts, A0=None, B0=None, C0=None, *, device=-1, retu
     `single` D: O, E float32; A, B, C, errHist float64), r <= 16."""
     o = make_opts(opts)
     _check_observed(observed)
-    if np.asarray(D).dtype == np.float32:
-        if observed is not None or holdout is not None:
-            raise TritdError(_lib.TRITD_ERR_UNSUPPORTED,
-                             "observed (a mask) is implemented for a double D only")
-        return _admm_f32(D, r, o, opts, A0, B0, C0, device, return_E, return_iters)
-    D = _fortran(D)
-    n1, n2, n3 = _size3(D)
-    r = int(r)
-    obs = None
-    if observed is not None:
-        obs = _observed_bytes(observed, D.shape)
-        if virtual_shards and virtual_shards > 1:
-            raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
-    hold = None
-    if holdout is not None:
-        hold = _observed_bytes(holdout, D.shape, "D", "holdout")
-        if virtual_shards and virtual_shards > 1:
-            raise ValueError("holdout with virtual_shards: use set_devices([d] * P) and device=-1")
-    if A0 is None or B0 is None or C0 is None:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
-    else:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, dict(A0=A0, B0=B0, C0=C0))
-    A = np.zeros((n1, r, r), order="F")
-    B = np.zeros((r, n2, r), order="F")
-    Cf = np.zeros((r, r, n3), order="F")
-    O = np.zeros((n1, n2, n3), order="F")
+    f32 = np.asarray(D).dtype == np.float32
+    if f32 and (observed is not None or holdout is not None):
+        raise TritdError(_lib.TRITD_ERR_UNSUPPORTED,
+                         "observed (a mask) is implemented for a double D only")
+    D = np.asfortranarray(D, dtype=np.float32) if f32 else _fortran(D)
+    _size3(D)  # (at most 3-D: refused before the masks are looked at)
+    obs, hold = _masks(observed, holdout, D, "D", virtual_shards)
     # E only when asked for (a full tensor more to bring back from the device)
-    E = np.zeros((n1, n2, n3), order="F") if return_E else None
-    errHist = np.zeros(max(o.maxIter, 1))
-    k = _lib.i32(0)
-    if hold is not None:
-        Ab, Bb, Cb = np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cf)
-        valHist, valHist1 = np.zeros(max(o.maxIter, 1)), np.zeros(max(o.maxIter, 1))
-        best, why = _lib.i32(0), _lib.i32(0)
-        check_flags(lib.tritd_admm_holdout_f64(_ptr(D), _ptr(obs), _ptr(hold), n1, n2, n3, r,
-                                               C.byref(o), int(patience), int(val_norm), _ptr(A0),
-                                               _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf),
-                                               _ptr(O), _ptr(E), _ptr(errHist), C.byref(k), _ptr(Ab),
-                                               _ptr(Bb), _ptr(Cb), _ptr(valHist), _ptr(valHist1),
-                                               C.byref(best), C.byref(why), int(device)),
-                    "triple_decomp_ADMM")
-        count = _holdout_count(hold, obs, D)
-        out = [A, B, Cf, O, errHist[: k.value].copy()]
-        if return_E:
-            out.append(E)
-        if return_iters:
-            out.append(k.value)
-        out.append(dict(valHist=valHist[: k.value].copy(), valHist1=valHist1[: k.value].copy(),
-                        best_iter=best.value, stop_reason=why.value, A_best=Ab, B_best=Bb,
-                        C_best=Cb, holdout_count=count))
-        return tuple(out)
-    if virtual_shards and virtual_shards > 1:
-        check_flags(lib.tritd_admm_sharded_virtual_f64(_ptr(D), n1, n2, n3, r, C.byref(o), _ptr(A0),
-                                                 _ptr(B0), _ptr(C0), int(virtual_shards), _ptr(A),
-                                                 _ptr(B), _ptr(Cf), _ptr(O), _ptr(E),
-                                                 _ptr(errHist), C.byref(k), int(device)), "triple_decomp_ADMM")
-    elif obs is not None:
-        check_flags(lib.tritd_admm_masked_f64(_ptr(D), _ptr(obs), n1, n2, n3, r, C.byref(o), _ptr(A0),
-                                              _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(O),
-                                              _ptr(E), _ptr(errHist), C.byref(k), int(device)),
-                    "triple_decomp_ADMM")
-    else:
-        check_flags(lib.tritd_admm_f64(_ptr(D), n1, n2, n3, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
-                                 _ptr(A), _ptr(B), _ptr(Cf), _ptr(O), _ptr(E), _ptr(errHist),
-                                 C.byref(k), int(device)), "triple_decomp_ADMM")
-    errHist = errHist[: k.value].copy()  # :68 errHist = errHist(1:k)
-    out = [A, B, Cf, O, errHist]
-    if return_E:
-        out.append(E)
-    if return_iters:
-        out.append(k.value)
-    return tuple(out)
-
-
-def _admm_f32(D, r, o, opts, A0, B0, C0, device, return_E, return_iters):
-    D = np.asfortranarray(D, dtype=np.float32)
-    n1, n2, n3 = _size3(D)
-    r = int(r)
-    if A0 is None or B0 is None or C0 is None:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
-    else:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, dict(A0=A0, B0=B0, C0=C0))
-    A = np.zeros((n1, r, r), order="F")
-    B = np.zeros((r, n2, r), order="F")
-    Cf = np.zeros((r, r, n3), order="F")
-    O = np.zeros((n1, n2, n3), order="F", dtype=np.float32)
-    E = np.zeros((n1, n2, n3), order="F", dtype=np.float32) if return_E else None
-    errHist = np.zeros(max(o.maxIter, 1))
-    k = _lib.i32(0)
-    check_flags(lib.tritd_admm_f32(_ptr(D), n1, n2, n3, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
-                             _ptr(A), _ptr(B), _ptr(Cf), _ptr(O), _ptr(E), _ptr(errHist),
-                             C.byref(k), int(device)), "triple_decomp_ADMM")
-    out = [A, B, Cf, O, errHist[: k.value].copy()]
-    if return_E:
-        out.append(E)
-    if return_iters:
-        out.append(k.value)
-    return tuple(out)
+    s = _OneShot(D, r, o.maxIter, opts, A0, B0, C0, tensors=(True, return_E), obs=obs, hold=hold)
+    s.solve(_ADMM, "triple_decomp_ADMM", (C.byref(o),), device, (int(patience), int(val_norm)),
+            virtual_shards, form="f32" if f32 else None)
+    # :68 errHist = errHist(1:k)
+    return s.result(s.tensors[:1], s.tensors[1:] * bool(return_E) + [_K] * bool(return_iters))
 
 
 # the name video_triple_comparison.m:54 calls (unresolvable in the reference)
@@ -336,52 +341,16 @@ def triple_decomp_ncvx(X, r, rho, lam, gamma_A, epsilon, p, theta, maxIter, tol,
     kept) and ``holdout_count``.  ``patience = p > 0`` stops the loop at k once
     ``k - best_iter >= p``, like a break of :67."""
     X = _fortran(X)
-    n1, n2, n3 = _size3(X)
-    r = int(r)
+    _size3(X)
     maxIter = int(maxIter)
-    obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
-    hold = _observed_bytes(holdout, X.shape, "X", "holdout") if holdout is not None else None
+    obs, hold = _masks(observed, holdout, X, "X")
     if hold is None and (patience != 0 or val_norm != 2):
         raise ValueError("patience and val_norm need holdout")
-    if A0 is None or B0 is None or C0 is None:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r)
-    else:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, dict(A0=A0, B0=B0, C0=C0))
-    A = np.zeros((n1, r, r), order="F")
-    B = np.zeros((r, n2, r), order="F")
-    Cf = np.zeros((r, r, n3), order="F")
-    O = np.zeros((n1, n2, n3), order="F")
-    errHist = np.zeros(max(maxIter, 1))
-    k = _lib.i32(0)
-    prm = (float(rho), float(lam), float(gamma_A), float(epsilon), float(p), float(theta), maxIter,
-           float(tol), _ptr(A0), _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(O),
-           _ptr(errHist), C.byref(k), int(device))
-    if hold is not None:
-        Ab, Bb, Cb = np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cf)
-        valHist, valHist1 = np.zeros(max(maxIter, 1)), np.zeros(max(maxIter, 1))
-        best, why = _lib.i32(0), _lib.i32(0)
-        check_flags(lib.tritd_ncvx_holdout_f64(_ptr(X), _ptr(obs), _ptr(hold), n1, n2, n3, r,
-                                               *prm[:8], int(patience), int(val_norm), *prm[8:17],
-                                               _ptr(Ab), _ptr(Bb), _ptr(Cb), _ptr(valHist),
-                                               _ptr(valHist1), C.byref(best), C.byref(why),
-                                               int(device)), "triple_decomp_ADMM_outlier")
-        count = _holdout_count(hold, obs, X)
-        out = [A, B, Cf, O, errHist[: k.value].copy()]
-        if return_iters:
-            out.append(k.value)
-        out.append(dict(valHist=valHist[: k.value].copy(), valHist1=valHist1[: k.value].copy(),
-                        best_iter=best.value, stop_reason=why.value, A_best=Ab, B_best=Bb,
-                        C_best=Cb, holdout_count=count))
-        return tuple(out)
-    if obs is not None:
-        check_flags(lib.tritd_ncvx_masked_f64(_ptr(X), _ptr(obs), n1, n2, n3, r, *prm),
-                    "triple_decomp_ADMM_outlier")
-    else:
-        check_flags(lib.tritd_ncvx_f64(_ptr(X), n1, n2, n3, r, *prm), "triple_decomp_ADMM_outlier")
-    out = [A, B, Cf, O, errHist[: k.value].copy()]
-    if return_iters:
-        out.append(k.value)
-    return tuple(out)
+    s = _OneShot(X, r, maxIter, None, A0, B0, C0, tensors=(True,), obs=obs, hold=hold)
+    s.solve(_NCVX, "triple_decomp_ADMM_outlier",
+            (float(rho), float(lam), float(gamma_A), float(epsilon), float(p), float(theta), maxIter,
+             float(tol)), device, (int(patience), int(val_norm)))
+    return s.result(s.tensors, [_K] * bool(return_iters))
 
 
 def triple_decomp_ADMM_outlier(*args, **kw):
@@ -439,63 +408,11 @@ def triple_decomp_ALS(X, r, opts, A0=None, B0=None, C0=None, *, device=-1, retur
     schedule as P shards on one device.  fp64, r <= 8."""
     o = make_als_opts(opts)
     X = _fortran(X)
-    n1, n2, n3 = _size3(X)
-    r = int(r)
-    obs = None
-    if observed is not None:
-        obs = _observed_bytes(observed, X.shape, "X")
-        if virtual_shards and virtual_shards > 1:
-            raise ValueError("observed with virtual_shards: use set_devices([d] * P) and device=-1")
-    hold = None
-    if holdout is not None:
-        hold = _observed_bytes(holdout, X.shape, "X", "holdout")
-        if virtual_shards and virtual_shards > 1:
-            raise ValueError("holdout with virtual_shards: use set_devices([d] * P) and device=-1")
-    if A0 is None or B0 is None or C0 is None:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, opts)
-    else:
-        A0, B0, C0 = initial_factors(n1, n2, n3, r, dict(A0=A0, B0=B0, C0=C0))
-    A = np.zeros((n1, r, r), order="F")
-    B = np.zeros((r, n2, r), order="F")
-    Cf = np.zeros((r, r, n3), order="F")
-    errHist = np.zeros(max(o.maxIter, 1))
-    k = _lib.i32(0)
-    if hold is not None:
-        Ab, Bb, Cb = np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cf)
-        valHist = np.zeros(max(o.maxIter, 1))
-        best, why = _lib.i32(0), _lib.i32(0)
-        check_flags(lib.tritd_als_holdout_f64(_ptr(X), _ptr(obs), _ptr(hold), n1, n2, n3, r,
-                                              C.byref(o), int(patience), _ptr(A0), _ptr(B0),
-                                              _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf), _ptr(errHist),
-                                              C.byref(k), _ptr(Ab), _ptr(Bb), _ptr(Cb),
-                                              _ptr(valHist), C.byref(best), C.byref(why),
-                                              int(device)), "triple_decomp_ALS")
-        count = _holdout_count(hold, obs, X)
-        out = [A, B, Cf, errHist[: k.value].copy()]
-        if return_iters:
-            out.append(k.value)
-        out.append(dict(valHist=valHist[: k.value].copy(), best_iter=best.value,
-                        stop_reason=why.value, A_best=Ab, B_best=Bb, C_best=Cb,
-                        holdout_count=count))
-        return tuple(out)
-    if virtual_shards and virtual_shards > 1:
-        check_flags(lib.tritd_als_sharded_virtual_f64(_ptr(X), n1, n2, n3, r, C.byref(o), _ptr(A0),
-                                                _ptr(B0), _ptr(C0), int(virtual_shards), _ptr(A),
-                                                _ptr(B), _ptr(Cf), _ptr(errHist), C.byref(k),
-                                                int(device)), "triple_decomp_ALS")
-    elif obs is not None:
-        check_flags(lib.tritd_als_masked_f64(_ptr(X), _ptr(obs), n1, n2, n3, r, C.byref(o), _ptr(A0),
-                                             _ptr(B0), _ptr(C0), _ptr(A), _ptr(B), _ptr(Cf),
-                                             _ptr(errHist), C.byref(k), int(device)),
-                    "triple_decomp_ALS")
-    else:
-        check_flags(lib.tritd_als_f64(_ptr(X), n1, n2, n3, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
-                                _ptr(A), _ptr(B), _ptr(Cf), _ptr(errHist), C.byref(k),
-                                int(device)), "triple_decomp_ALS")
-    out = [A, B, Cf, errHist[: k.value].copy()]  # :21 errHist = errHist(1:k)
-    if return_iters:
-        out.append(k.value)
-    return tuple(out)
+    _size3(X)
+    obs, hold = _masks(observed, holdout, X, "X", virtual_shards)
+    s = _OneShot(X, r, o.maxIter, opts, A0, B0, C0, tensors=(), obs=obs, hold=hold, l1=False)
+    s.solve(_ALS, "triple_decomp_ALS", (C.byref(o),), device, (int(patience),), virtual_shards)
+    return s.result((), [_K] * bool(return_iters))  # :21 errHist = errHist(1:k)
 
 
 def triple_product(A, B, C_, model="cp"):
@@ -603,7 +520,108 @@ def buildH(A, B):
 # ---------------------------------------------------------------------------
 # Sessions: device-resident loop (bench, multi-GPU)
 # ---------------------------------------------------------------------------
-class Session:
+def _marshal_shard(data, device_ptr, ld, rows, observed, holdout, what, dtype, flags):
+    """A shard's data and masks for a session creator: a host array (made
+    column-major ``dtype``; the masks logical arrays of its shape) or a device
+    pointer (the masks device pointers too), ``observed`` possibly "nan".
+    -> (data pointer, ld, observed pointer, holdout pointer, flags, the host
+    arrays to keep alive over the call)."""
+    if device_ptr is not None:
+        ld = ld if ld is not None else rows
+        hptr = C.c_void_p(int(holdout)) if holdout is not None else None
+        return (C.c_void_p(int(device_ptr)), int(ld), _device_mask(observed), hptr,
+                flags | _lib.SESSION_D_ON_DEVICE, ())
+    data = np.asfortranarray(data, dtype=dtype)
+    ld = ld if ld is not None else data.shape[0]
+    obs = _observed_bytes(observed, data.shape, what) if observed is not None else None
+    hold = _observed_bytes(holdout, data.shape, what, "holdout") if holdout is not None else None
+    return _ptr(data), int(ld), _ptr(obs), _ptr(hold), flags, (data, obs, hold)
+
+
+class _SessionBase:
+    """What ``Session`` and ``AlsSession`` share: the creation of a shard's
+    session and the calls that differ only in the C symbol's prefix."""
+
+    _prefix = ""  # "tritd_session_" / "tritd_als_session_"
+
+    def _fn(self, name):
+        return getattr(lib, self._prefix + name)
+
+    def _create(self, r, o, start, n1, n2, n3, i0, i1, data, device_ptr, ld, device, comm, observed,
+                holdout, what, dtype=np.float64, flags=0, holdout_args=(), tail=(), form=None):
+        """Create the session of form "" (plain), "masked" or "holdout" (what
+        the masks imply) unless ``form`` names another creator.  ``o``: the
+        tritd_opts; ``holdout_args`` follow it in a holdout creator; ``tail``
+        follows the flags."""
+        i1 = n1 if i1 is None else i1
+        start = [_fortran(a) for a in start]
+        dptr, ld, optr, hptr, flags, keep = _marshal_shard(data, device_ptr, ld, i1 - i0, observed,
+                                                           holdout, what, dtype, flags)
+        self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
+        self.maxIter = o.maxIter
+        if form is None:
+            form = "holdout" if hptr is not None else "masked" if optr is not None else ""
+        args = [C.byref(self._s), int(device), dptr]
+        if form:
+            args.append(optr)
+        if hptr is not None:
+            args.append(hptr)
+        args += [ld, n1, n2, n3, i0, i1, r, C.byref(o)]
+        if hptr is not None:
+            args += holdout_args
+        args += [_ptr(a) for a in start]
+        args += [comm.handle if comm is not None else None, flags, *tail]
+        # (`keep` holds the host arrays until the creator has copied the shard)
+        check(self._fn("create_" + form if form else "create")(*args))
+
+    def _factors(self):
+        """zeroed A, B, C of the whole problem's shapes (column-major)"""
+        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
+        return (np.zeros((n1, r, r), order="F"), np.zeros((r, n2, r), order="F"),
+                np.zeros((r, r, n3), order="F"))
+
+    def mask_info(self):
+        """(whether the session has a mask, observed entries of its shard)"""
+        m, c = _lib.i32(0), _lib.i64(0)
+        check(self._fn("mask_info")(self._s, C.byref(m), C.byref(c)))
+        return bool(m.value), c.value
+
+    def get_best(self):
+        """The factors of the best iterate (after iteration best_iter for the
+        ADMM, the ones iteration best_iter started with for the ALS and the
+        nonconvex solver), shaped like those of ``get()``: tritd_session_get_best
+        / tritd_als_session_get_best."""
+        A, B, Cf = self._factors()
+        check(self._fn("get_best")(self._s, _ptr(A), _ptr(B), _ptr(Cf)))
+        return dict(A=A, B=B, C=Cf)
+
+    def run(self, iters):
+        check(self._fn("run")(self._s, int(iters)))
+
+    def sync(self):
+        d, s = _lib.i32(0), _lib.i32(0)
+        check(self._fn("sync")(self._s, C.byref(d), C.byref(s)))
+        return d.value, bool(s.value)
+
+    def flags(self):
+        """TRITD_FLAG_* raised so far (read at each sync)."""
+        f = C.c_uint32(0)
+        check(self._fn("flags")(self._s, C.byref(f)))
+        return f.value
+
+    def close(self):
+        if self._s:
+            self._fn("destroy")(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Session(_SessionBase):
     """One mode-1 shard [i0, i1) of an n1 x n2 x n3 problem on one GPU.
 
     D is either a host numpy array holding the shard (column-major, leading
@@ -626,16 +644,14 @@ class Session:
     and ``holdout_info()`` the held-out count of the shard, ``||H o Omega o D||``
     and ``sum |H o Omega o D|``."""
 
+    _prefix = "tritd_session_"
+
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, D=None,
                  d_device_ptr=None, ldD=None, device=0, comm=None, dtype=None, probe=True,
                  observed=None, holdout=None, patience=0, val_norm=2):
         self._s = C.c_void_p()
         self._holdout = holdout is not None
         o = make_opts(opts)
-        i1 = n1 if i1 is None else i1
-        A0 = _fortran(A0)
-        B0 = _fortran(B0)
-        C0 = _fortran(C0)
         if dtype is None:
             dtype = np.asarray(D).dtype if D is not None else np.float64
         self.f32 = np.dtype(dtype) == np.float32
@@ -644,43 +660,10 @@ class Session:
             flags |= _lib.SESSION_PROBE
         if d_device_ptr is not None:
             _lib.check_one_runtime("Session(d_device_ptr=...)")
-            dptr = C.c_void_p(int(d_device_ptr))
-            flags |= _lib.SESSION_D_ON_DEVICE
-            ldD = ldD if ldD is not None else (i1 - i0)
-            optr = _device_mask(observed)
-            hptr = C.c_void_p(int(holdout)) if holdout is not None else None
-        else:
-            D = np.asfortranarray(D, dtype=np.float32 if self.f32 else np.float64)
-            dptr = _ptr(D)
-            ldD = ldD if ldD is not None else D.shape[0]
-            obs = _observed_bytes(observed, D.shape) if observed is not None else None
-            optr = _ptr(obs)
-            hold = _observed_bytes(holdout, D.shape, "D", "holdout") if holdout is not None else None
-            hptr = _ptr(hold)
-        self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
-        self.maxIter = o.maxIter
-        if hptr is not None:
-            check(lib.tritd_session_create_holdout(C.byref(self._s), int(device), dptr, optr, hptr,
-                                                   int(ldD), n1, n2, n3, i0, i1, r, C.byref(o),
-                                                   int(patience), int(val_norm), _ptr(A0), _ptr(B0),
-                                                   _ptr(C0),
-                                                   comm.handle if comm is not None else None, flags))
-            return
-        if optr is not None:
-            check(lib.tritd_session_create_masked(C.byref(self._s), int(device), dptr, optr, int(ldD),
-                                                  n1, n2, n3, i0, i1, r, C.byref(o), _ptr(A0),
-                                                  _ptr(B0), _ptr(C0),
-                                                  comm.handle if comm is not None else None, flags))
-            return
-        check(lib.tritd_session_create(C.byref(self._s), int(device), dptr, int(ldD), n1, n2, n3,
-                                       i0, i1, r, C.byref(o), _ptr(A0), _ptr(B0), _ptr(C0),
-                                       comm.handle if comm is not None else None, flags))
+        self._create(r, o, (A0, B0, C0), n1, n2, n3, i0, i1, D, d_device_ptr, ldD, device, comm,
+                     observed, holdout, "D", np.float32 if self.f32 else np.float64, flags,
+                     (int(patience), int(val_norm)))
 
-    def mask_info(self):
-        """(whether the session has a mask, observed entries of its shard)"""
-        m, c = _lib.i32(0), _lib.i64(0)
-        check(lib.tritd_session_mask_info(self._s, C.byref(m), C.byref(c)))
-        return bool(m.value), c.value
 
     def holdout_info(self):
         """(held-out entries of the shard, ||H o Omega o D|| and sum |H o Omega o D|
@@ -698,15 +681,6 @@ class Session:
         return dict(valHist=vh[:k].copy(), valHist1=vh1[:k].copy(), best_iter=best.value,
                     stop_reason=why.value)
 
-    def get_best(self):
-        """The factors after iteration best_iter, shaped like those of ``get()``:
-        tritd_session_get_best."""
-        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
-        A = np.zeros((n1, r, r), order="F")
-        B = np.zeros((r, n2, r), order="F")
-        Cf = np.zeros((r, r, n3), order="F")
-        check(lib.tritd_session_get_best(self._s, _ptr(A), _ptr(B), _ptr(Cf)))
-        return dict(A=A, B=B, C=Cf)
 
     def holdout_ms(self):
         """(score kernel ms, ms from the end of K5 to the end of the iteration)
@@ -715,26 +689,11 @@ class Session:
         check(lib.tritd_session_holdout_ms(self._s, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def run(self, iters):
-        check(lib.tritd_session_run(self._s, int(iters)))
-
-    def sync(self):
-        d, s = _lib.i32(0), _lib.i32(0)
-        check(lib.tritd_session_sync(self._s, C.byref(d), C.byref(s)))
-        return d.value, bool(s.value)
-
-    def flags(self):
-        """TRITD_FLAG_* raised so far (read at each sync)."""
-        f = C.c_uint32(0)
-        check(lib.tritd_session_flags(self._s, C.byref(f)))
-        return f.value
 
     def get(self):
-        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
+        n2, n3 = self.n2, self.n3
         nl = self.i1 - self.i0
-        A = np.zeros((n1, r, r), order="F")
-        B = np.zeros((r, n2, r), order="F")
-        Cf = np.zeros((r, r, n3), order="F")
+        A, B, Cf = self._factors()
         dt = np.float32 if self.f32 else np.float64
         O = np.zeros((nl, n2, n3), order="F", dtype=dt)
         E = np.zeros((nl, n2, n3), order="F", dtype=dt)
@@ -794,19 +753,9 @@ class Session:
         check(lib.tritd_session_kernel_ms(self._s, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return dict(fused_update=a.value, mode3=b.value, iteration=c.value, samples=n.value)
 
-    def close(self):
-        if self._s:
-            lib.tritd_session_destroy(self._s)
-            self._s = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class AlsSession:
+class AlsSession(_SessionBase):
     """Steppable device-resident triple_decomp_ALS on one mode-1 shard
     (bench; one process per GPU with ``comm``).  ``quiet`` drops the
     every-5-iterations progress line and its host synchronisation.
@@ -829,6 +778,8 @@ class AlsSession:
     ``holdout_info()`` the held-out count of the shard and ``||H o Omega o X||``.
     ``ncvx`` with ``holdout`` is refused (TRITD_ERR_UNSUPPORTED)."""
 
+    _prefix = "tritd_als_session_"
+
     def __init__(self, r, opts, A0, B0, C0, *, n1, n2, n3, i0=0, i1=None, X=None,
                  x_device_ptr=None, ldX=None, device=0, comm=None, quiet=True, observed=None,
                  ncvx=None, holdout=None, patience=0):
@@ -836,44 +787,9 @@ class AlsSession:
         self._holdout = holdout is not None
         if ncvx is not None:
             ncvx = [float(ncvx[k]) for k in ("rho", "lam", "gamma_A", "epsilon", "p", "theta")]
-        o = make_als_opts(opts)
-        i1 = n1 if i1 is None else i1
-        A0, B0, C0 = _fortran(A0), _fortran(B0), _fortran(C0)
-        flags = 0
-        if x_device_ptr is not None:
-            xptr = C.c_void_p(int(x_device_ptr))
-            flags |= _lib.SESSION_D_ON_DEVICE
-            ldX = ldX if ldX is not None else (i1 - i0)
-            optr = _device_mask(observed)
-            hptr = C.c_void_p(int(holdout)) if holdout is not None else None
-        else:
-            X = _fortran(X)
-            xptr = _ptr(X)
-            ldX = ldX if ldX is not None else X.shape[0]
-            obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
-            optr = _ptr(obs)
-            hold = _observed_bytes(holdout, X.shape, "X", "holdout") if holdout is not None else None
-            hptr = _ptr(hold)
-        self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
-        self.maxIter = o.maxIter
-        if hptr is not None:
-            check(lib.tritd_als_session_create_holdout(C.byref(self._s), int(device), xptr, optr,
-                                                       hptr, int(ldX), n1, n2, n3, i0, i1, r,
-                                                       C.byref(o), int(patience), _ptr(A0),
-                                                       _ptr(B0), _ptr(C0),
-                                                       comm.handle if comm is not None else None,
-                                                       flags, int(bool(quiet))))
-        elif optr is not None:
-            check(lib.tritd_als_session_create_masked(C.byref(self._s), int(device), xptr, optr,
-                                                      int(ldX), n1, n2, n3, i0, i1, r, C.byref(o),
-                                                      _ptr(A0), _ptr(B0), _ptr(C0),
-                                                      comm.handle if comm is not None else None,
-                                                      flags, int(bool(quiet))))
-        else:
-            check(lib.tritd_als_session_create(C.byref(self._s), int(device), xptr, int(ldX), n1,
-                                               n2, n3, i0, i1, r, C.byref(o), _ptr(A0), _ptr(B0),
-                                               _ptr(C0), comm.handle if comm is not None else None,
-                                               flags, int(bool(quiet))))
+        self._create(r, make_als_opts(opts), (A0, B0, C0), n1, n2, n3, i0, i1, X, x_device_ptr, ldX,
+                     device, comm, observed, holdout, "X", holdout_args=(int(patience),),
+                     tail=(int(bool(quiet)),))
         if ncvx is not None:
             self.set_ncvx(*ncvx)
 
@@ -890,11 +806,6 @@ class AlsSession:
         check(lib.tritd_als_session_get_O(self._s, _ptr(O), self.i1 - self.i0))
         return O
 
-    def mask_info(self):
-        """(whether the session has a mask, observed entries of its shard)"""
-        m, c = _lib.i32(0), _lib.i64(0)
-        check(lib.tritd_als_session_mask_info(self._s, C.byref(m), C.byref(c)))
-        return bool(m.value), c.value
 
     def holdout_info(self):
         """(held-out entries of the shard, ||H o Omega o X|| over all shards)"""
@@ -902,35 +813,10 @@ class AlsSession:
         check(lib.tritd_als_session_holdout_info(self._s, C.byref(c), C.byref(nrm)))
         return c.value, nrm.value
 
-    def get_best(self):
-        """The factors iteration best_iter started with, shaped like those of
-        ``get()``: tritd_als_session_get_best."""
-        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
-        A = np.zeros((n1, r, r), order="F")
-        B = np.zeros((r, n2, r), order="F")
-        Cf = np.zeros((r, r, n3), order="F")
-        check(lib.tritd_als_session_get_best(self._s, _ptr(A), _ptr(B), _ptr(Cf)))
-        return dict(A=A, B=B, C=Cf)
 
-    def run(self, iters):
-        check(lib.tritd_als_session_run(self._s, int(iters)))
-
-    def sync(self):
-        d, s = _lib.i32(0), _lib.i32(0)
-        check(lib.tritd_als_session_sync(self._s, C.byref(d), C.byref(s)))
-        return d.value, bool(s.value)
-
-    def flags(self):
-        """TRITD_FLAG_* raised so far (read at each sync)."""
-        f = C.c_uint32(0)
-        check(lib.tritd_als_session_flags(self._s, C.byref(f)))
-        return f.value
 
     def get(self):
-        r, n1, n2, n3 = self.r, self.n1, self.n2, self.n3
-        A = np.zeros((n1, r, r), order="F")
-        B = np.zeros((r, n2, r), order="F")
-        Cf = np.zeros((r, r, n3), order="F")
+        A, B, Cf = self._factors()
         eh = np.zeros(max(self.maxIter, 1))
         k = _lib.i32(0)
         check(lib.tritd_als_session_get(self._s, _ptr(A), _ptr(B), _ptr(Cf), _ptr(eh), C.byref(k)))
@@ -953,16 +839,6 @@ class AlsSession:
                                               C.byref(n)))
         return dict(fit=a.value, mode3=b.value, iteration=c.value, samples=n.value)
 
-    def close(self):
-        if self._s:
-            lib.tritd_als_session_destroy(self._s)
-            self._s = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class NcvxSession(AlsSession):
@@ -985,30 +861,10 @@ class NcvxSession(AlsSession):
         if holdout is None:
             raise ValueError("NcvxSession needs holdout (AlsSession(ncvx=) runs without one)")
         prm = [float(ncvx[k]) for k in ("rho", "lam", "gamma_A", "epsilon", "p", "theta")]
-        o = make_als_opts(opts)
-        i1 = n1 if i1 is None else i1
-        A0, B0, C0 = _fortran(A0), _fortran(B0), _fortran(C0)
-        flags = 0
-        if x_device_ptr is not None:
-            xptr = C.c_void_p(int(x_device_ptr))
-            flags |= _lib.SESSION_D_ON_DEVICE
-            ldX = ldX if ldX is not None else (i1 - i0)
-            optr = _device_mask(observed)
-            hptr = C.c_void_p(int(holdout))
-        else:
-            X = _fortran(X)
-            xptr = _ptr(X)
-            ldX = ldX if ldX is not None else X.shape[0]
-            obs = _observed_bytes(observed, X.shape, "X") if observed is not None else None
-            optr = _ptr(obs)
-            hold = _observed_bytes(holdout, X.shape, "X", "holdout")
-            hptr = _ptr(hold)
-        self.n1, self.n2, self.n3, self.i0, self.i1, self.r = n1, n2, n3, i0, i1, r
-        self.maxIter = o.maxIter
-        check(lib.tritd_als_session_create_ncvx_holdout(
-            C.byref(self._s), int(device), xptr, optr, hptr, int(ldX), n1, n2, n3, i0, i1, r,
-            C.byref(o), int(patience), int(val_norm), *prm, _ptr(A0), _ptr(B0), _ptr(C0),
-            comm.handle if comm is not None else None, flags, int(bool(quiet))))
+        self._create(r, make_als_opts(opts), (A0, B0, C0), n1, n2, n3, i0, i1, X, x_device_ptr, ldX,
+                     device, comm, observed, holdout, "X",
+                     holdout_args=(int(patience), int(val_norm), *prm), tail=(int(bool(quiet)),),
+                     form="ncvx_holdout")
 
     def get_val(self):
         """dict(valHist, valHist1, best_iter, stop_reason): tritd_als_session_get_val2."""
