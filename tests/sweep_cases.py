@@ -14,6 +14,13 @@ compact and the dense tile forms, and well conditioned in fp64 and fp32.
 Shapes (35 + r%3, 19 + r%5, 33 + r%4): every mode ragged against the 16-row
 and 16-t tiles, more than one tile in i and in t.
 
+One more case, TALL, stands beside the ranks wherever a function here takes a
+case: 97 x 83 x 85 at r = 7 (padded rank 64; n1p = 112, n2 = 83, n3p = 96).
+Every sweep shape keeps rows * RP^2 within the 327 680 up to which a factor's
+apply and Gram are one launch (80 rows at RP = 64; csrc/kernels.h
+apply_gram_small), so only this case takes the two-launch branch of all three
+factor updates, and with it the side jobs without a deferred Gram.
+
 References are computed once per process and shared (lru_cache); callers must
 not modify the arrays they get.
 """
@@ -38,8 +45,21 @@ TILE_CAP = 28
 TILE_SHARE_MIN = 0.10
 
 
+TALL = "tall"
+TALL_SHAPE, TALL_RANK = (97, 83, 85), 7
+
+
 def e_active_shape(r):
     return (35 + r % 3, 19 + r % 5, 33 + r % 4)
+
+
+def case_rank(case):
+    """A case is a rank r of RANKS (at e_active_shape(r)) or TALL."""
+    return TALL_RANK if case == TALL else case
+
+
+def case_shape(case):
+    return TALL_SHAPE if case == TALL else e_active_shape(case)
 
 
 def active_lambda(D):
@@ -53,9 +73,10 @@ _SEEDS = {("qi", 6): 46, ("qi", 7): 47}
 
 
 @functools.lru_cache(maxsize=None)
-def _case64(r, model):
+def _case64(case, model):
     from tritd import synth
-    d = synth.low_rank_plus_outliers(*e_active_shape(r), r, seed=_SEEDS.get((model, r), r),
+    r = case_rank(case)
+    d = synth.low_rank_plus_outliers(*case_shape(case), r, seed=_SEEDS.get((model, case), r),
                                      init_seed=r + 100, model=model)
     opts = dict(synth.TRAFFIC_OPTS, maxIter=ITERS)
     opts["lambda"] = active_lambda(d["D"])
@@ -64,13 +85,13 @@ def _case64(r, model):
     return d, opts
 
 
-def e_active_case(r, dtype=np.float64, model="cp"):
+def e_active_case(case, dtype=np.float64, model="cp"):
     """dict(D, Lstar, A0, B0, C0, opts, r): D of `dtype` (column-major), lambda
     from the fp64 D for either dtype so both precisions solve the same problem;
     Lstar is the generator's low-rank part in fp64 (the driver's RRE reference)."""
-    d, opts = _case64(r, model)
+    d, opts = _case64(case, model)
     return dict(D=np.asfortranarray(d["D"], dtype=dtype), Lstar=d["Lstar"], A0=d["A0"], B0=d["B0"],
-                C0=d["C0"], opts=dict(opts), r=r)
+                C0=d["C0"], opts=dict(opts), r=case_rank(case))
 
 
 def as_ref(t):
@@ -79,11 +100,11 @@ def as_ref(t):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_ref(r, model="cp", iters=ITERS):
-    """The numpy oracle on e_active_case(r) (fp64)."""
+def oracle_ref(case, model="cp", iters=ITERS):
+    """The numpy oracle on e_active_case(case) (fp64)."""
     import tritd_oracle as orc
-    c = e_active_case(r, model=model)
-    return as_ref(orc.triple_decomp_ADMM(c["D"], r, dict(c["opts"], maxIter=iters), c["A0"],
+    c = e_active_case(case, model=model)
+    return as_ref(orc.triple_decomp_ADMM(c["D"], c["r"], dict(c["opts"], maxIter=iters), c["A0"],
                                          c["B0"], c["C0"]))
 
 
@@ -98,11 +119,11 @@ def cref_lib():
 
 
 @functools.lru_cache(maxsize=None)
-def c_ref(r, single, iters=ITERS):
-    """The C restatement on e_active_case(r): class double or class single."""
+def c_ref(case, single, iters=ITERS):
+    """The C restatement on e_active_case(case): class double or class single."""
     mod, lib = cref_lib()
-    c = e_active_case(r, np.float32 if single else np.float64)
-    return as_ref(mod.admm(lib, c["D"], r, dict(c["opts"], maxIter=iters), c["A0"], c["B0"],
+    c = e_active_case(case, np.float32 if single else np.float64)
+    return as_ref(mod.admm(lib, c["D"], c["r"], dict(c["opts"], maxIter=iters), c["A0"], c["B0"],
                            c["C0"]))
 
 

@@ -91,7 +91,7 @@ def test_rccl_session_batches_and_disp(tritd):
 @pytest.mark.parametrize("fused", ["0", "1"])
 def test_single_gpu_schedules_match_golden(tritd, fused, monkeypatch):
     """TRITD_FUSED=1 (default): one stream, solves of C and A(k+1) inside
-    K2 / K5; 0: the side-stream schedule (Session::iterate_overlapped)."""
+    K2 / K5; 0: the side-stream schedule (Session::iterate_side)."""
     import tritd_oracle as orc
     monkeypatch.setenv("TRITD_FUSED", fused)
     g = load_golden("g17x16x20_r8")
@@ -113,7 +113,7 @@ def test_sharded_schedule_matches_phase_order(tritd, name, monkeypatch):
     """With a communicator the default schedule is the single-stream one
     (Session::iterate_fused: the solves of C and A(k+1) in an extra workgroup
     of K2 / K5, as a Gauss-Jordan sweep), TRITD_FUSED=0 the side-stream one
-    (Session::iterate_sharded), TRITD_SHOV=0 the phase-serial order.  The
+    (Session::iterate_side with its all-reduces), TRITD_SHOV=0 the phase-serial order.  The
     serial order refines solves C, A with Newton-Schulz (k_solve_ns), so the
     schedules agree to rounding, not bitwise; each is bitwise reproducible."""
     g = load_golden(name)

@@ -18,6 +18,14 @@ side-stream schedule (TRITD_FUSED=0), the dense-E form, the split t-walk,
 three virtual shards (12-13 rows each, straddling the 16-row tiles), a device
 set of one GPU twice, and a one-rank RCCL communicator.
 
+The tall case (sweep_cases.TALL: 97 x 83 x 85 at r = 7) runs the same forms
+past the one-launch threshold of apply + Gram, where every factor update is
+an apply and a Gram launch and no Gram is deferred to a side job: one-shot and
+3 + 7 on the fused schedule, the side-stream schedule, three virtual shards
+(32 / 32 / 33 rows: A^ small again, its Gram a side job of M2), the device set
+on the fused schedule and on the phase functions (TRITD_SHOV=0), and the
+one-rank communicator on the fused and on the side-stream schedule.
+
 Measured on an MI355X (one-shot call; worst of the schedules in brackets):
    r  nnz(E)   L        O        E        A        B        C        errHist(rel)
    1  0.127  3.1e-15  2.0e-15  1.9e-15  1.1e-14  3.9e-14  3.0e-14  2.2e-15
@@ -36,8 +44,10 @@ Measured on an MI355X (one-shot call; worst of the schedules in brackets):
   14  0.556  3.1e-14  5.1e-14  5.1e-14  3.1e-14  2.5e-14  3.0e-14  5.7e-16
   15  0.430  3.2e-14  9.7e-14  9.5e-14  3.9e-14  2.8e-14  4.2e-14  8.8e-16
   16  0.336  2.8e-14  1.2e-13  1.2e-13  4.1e-14  2.9e-14  4.1e-14  2.1e-15
+tall  0.168  5.9e-15  2.8e-15  1.7e-15  2.0e-14  2.3e-14  2.4e-14  4.0e-15  [L,O,E 5.9e-15; A,B,C 2.4e-14]
 Dense-tile totals of the 3 + 7 sessions (of 10 launches x tiles per launch):
-r=4 241 of 2160, r=6 547 of 1800, r=7 698 of 1920, r=11 904 of 1800, r=13 726 of 2040.
+r=4 241 of 2160, r=6 547 of 1800, r=7 698 of 1920, r=11 904 of 1800, r=13 726 of 2040,
+tall 5470 of 35040.
 """
 import numpy as np
 import pytest
@@ -50,6 +60,13 @@ pytestmark = pytest.mark.gpu
 
 SCHEDULE_RANKS = [4, 6, 7, 11, 13]
 NARROW = [r for r in SCHEDULE_RANKS if r * r <= 64]  # padded rank <= 64
+TALL = [sc.TALL]
+
+
+def with_env(cases, var):
+    """(case, None) under the ids the bare cases had, then the tall case with var=0."""
+    return ([pytest.param(c, None, id=str(c)) for c in cases + TALL]
+            + [pytest.param(sc.TALL, var, id="tall-%s=0" % var)])
 
 
 @pytest.fixture(scope="module")
@@ -65,16 +82,16 @@ def orc():
     return tritd_oracle
 
 
-def check(orc, got, r, label):
+def check(orc, got, case, label):
     """check_solution of test_gpu_parity.py, printing each figure before it asserts."""
-    ref = sc.oracle_ref(r)
+    ref = sc.oracle_ref(case)
     A, B, C, O, eh, E, k = got
     dev = dict(L=rel(orc.triple_product(A, B, C), orc.triple_product(ref["A"], ref["B"], ref["C"])),
                O=rel(O, ref["O"]), E=rel(E, ref["E"]), A=rel(A, ref["A"]), B=rel(B, ref["B"]),
                C=rel(C, ref["C"]))
     n = min(len(eh), len(ref["errHist"]))
     dev["eh"] = float(np.max(np.abs(eh[:n] - ref["errHist"][:n]) / ref["errHist"][:n])) if n else 0.0
-    print("  sweep r=%d %s k=%d nnz(E)=%.3f " % (r, label, k, sc.nnz_share(E))
+    print("  sweep r=%s %s k=%d nnz(E)=%.3f " % (case, label, k, sc.nnz_share(E))
           + " ".join("%s=%.1e" % kv for kv in dev.items()), flush=True)
     assert k == ref["k"] and len(eh) == ref["k"]
     assert np.any(ref["E"]) and np.any(E)
@@ -83,17 +100,17 @@ def check(orc, got, r, label):
     np.testing.assert_allclose(eh, ref["errHist"], rtol=TOL_ERR, atol=ATOL_ERR)
 
 
-def solve(tritd, r, **kw):
-    c = sc.e_active_case(r)
-    return tritd.triple_decomp_ADMM(c["D"], r, c["opts"], c["A0"], c["B0"], c["C0"], return_E=True,
-                                    return_iters=True, **kw)
+def solve(tritd, case, **kw):
+    c = sc.e_active_case(case)
+    return tritd.triple_decomp_ADMM(c["D"], c["r"], c["opts"], c["A0"], c["B0"], c["C0"],
+                                    return_E=True, return_iters=True, **kw)
 
 
-def session(tritd, r, comm=None):
-    c = sc.e_active_case(r)
+def session(tritd, case, comm=None):
+    c = sc.e_active_case(case)
     n1, n2, n3 = c["D"].shape
-    return tritd.Session(r, c["opts"], c["A0"], c["B0"], c["C0"], n1=n1, n2=n2, n3=n3, D=c["D"],
-                         device=0, comm=comm)
+    return tritd.Session(c["r"], c["opts"], c["A0"], c["B0"], c["C0"], n1=n1, n2=n2, n3=n3,
+                         D=c["D"], device=0, comm=comm)
 
 
 def session_result(s):
@@ -101,12 +118,12 @@ def session_result(s):
     return x["A"], x["B"], x["C"], x["O"], x["errHist"], x["E"], x["k"]
 
 
-@pytest.mark.parametrize("r", sc.RANKS)
+@pytest.mark.parametrize("r", sc.RANKS + (sc.TALL,))
 def test_one_shot(tritd, orc, r):
     check(orc, solve(tritd, r), r, "one-shot")
 
 
-@pytest.mark.parametrize("r", SCHEDULE_RANKS)
+@pytest.mark.parametrize("r", SCHEDULE_RANKS + TALL)
 def test_session_uneven_steps_and_both_storage_forms(tritd, orc, r):
     """3 + 7 iterations; the dense-tile counter shows that compact slots and
     dense tiles both occurred (0 < dense total < launches x tiles)."""
@@ -119,11 +136,11 @@ def test_session_uneven_steps_and_both_storage_forms(tritd, orc, r):
     finally:
         s.close()
     check(orc, got, r, "session 3+7")
-    print("  sweep r=%d dense tiles %d of %d x %d" % (r, dense, sc.ITERS, per), flush=True)
+    print("  sweep r=%s dense tiles %d of %d x %d" % (r, dense, sc.ITERS, per), flush=True)
     assert 0 < dense < sc.ITERS * per
 
 
-@pytest.mark.parametrize("r", NARROW)
+@pytest.mark.parametrize("r", NARROW + TALL)
 def test_side_stream_schedule(tritd, orc, r, monkeypatch):
     monkeypatch.setenv("TRITD_FUSED", "0")
     check(orc, solve(tritd, r), r, "TRITD_FUSED=0")
@@ -148,23 +165,29 @@ def test_split_t_walk(tritd, orc, r, monkeypatch):
     check(orc, solve(tritd, r), r, "TRITD_K5_TSPLIT=2")
 
 
-@pytest.mark.parametrize("r", SCHEDULE_RANKS)
+@pytest.mark.parametrize("r", SCHEDULE_RANKS + TALL)
 def test_virtual_shards(tritd, orc, r):
     check(orc, solve(tritd, r, virtual_shards=3), r, "virtual_shards=3")
 
 
-@pytest.mark.parametrize("r", SCHEDULE_RANKS)
-def test_device_set(tritd, orc, r):
+@pytest.mark.parametrize("r, shov", with_env(SCHEDULE_RANKS, "TRITD_SHOV"))
+def test_device_set(tritd, orc, r, shov, monkeypatch):
+    """TRITD_SHOV=0: the two shards run the phase functions, not the fused schedule."""
+    if shov is not None:
+        monkeypatch.setenv("TRITD_SHOV", "0")
     tritd.set_devices([0, 0])
     try:
         got = solve(tritd, r)
     finally:
         tritd.set_devices([])
-    check(orc, got, r, "set_devices([0,0])")
+    check(orc, got, r, "set_devices([0,0])" + (" TRITD_SHOV=0" if shov else ""))
 
 
-@pytest.mark.parametrize("r", SCHEDULE_RANKS)
-def test_rccl_one_rank(tritd, orc, r):
+@pytest.mark.parametrize("r, fused", with_env(SCHEDULE_RANKS, "TRITD_FUSED"))
+def test_rccl_one_rank(tritd, orc, r, fused, monkeypatch):
+    """TRITD_FUSED=0: the side-stream schedule with its all-reduces."""
+    if fused is not None:
+        monkeypatch.setenv("TRITD_FUSED", "0")
     comm = tritd.Comm(tritd.Comm.unique_id(), 1, 0, 0)
     try:
         s = session(tritd, r, comm)
@@ -175,4 +198,4 @@ def test_rccl_one_rank(tritd, orc, r):
             s.close()
     finally:
         comm.close()
-    check(orc, got, r, "rccl one rank")
+    check(orc, got, r, "rccl one rank" + (" TRITD_FUSED=0" if fused else ""))

@@ -2,7 +2,8 @@
 
 The GPU sweeps (tests/test_gpu_rank_sweep.py, test_gpu_f32.py, the ALS / Qi /
 nonconvex modules) compare at tight tolerances; a miss there must mean a
-kernel fault, not an ill-conditioned case.  For every rank r = 1..16:
+kernel fault, not an ill-conditioned case.  For every rank r = 1..16, and for
+the tall case (97 x 83 x 85 at r = 7, past the one-launch apply + Gram):
 
   * E is active and mixed: nnz(E) >= 0.5 % after 3 iterations, within
     10..70 % after 10; at least 10 % of the 16 x 16 (i, t) tiles hold 1..28
@@ -29,21 +30,32 @@ U32 = 2.0 ** -24
 U64 = 2.0 ** -52
 
 
-@pytest.mark.parametrize("r", sc.RANKS)
+CASES = sc.RANKS + (sc.TALL,)
+
+
+def test_tall_case_is_past_the_one_launch_threshold():
+    """rows * RP^2 > 327 680 for each of A^ (n1p rows), B^ (n2), C^ (n3p) at RP = 64."""
+    n1, n2, n3 = sc.case_shape(sc.TALL)
+    RP = -(-sc.TALL_RANK ** 2 // 16) * 16
+    assert RP == 64
+    assert min(-(-n1 // 16) * 16, n2, -(-n3 // 16) * 16) * RP * RP > 327680
+
+
+@pytest.mark.parametrize("r", CASES)
 def test_e_is_active_and_mixed(r):
-    shape = sc.e_active_shape(r)
+    shape = sc.case_shape(r)
     assert all(n % 16 for n in shape) and shape[0] > 16 and shape[2] > 16
     nnz3 = sc.nnz_share(sc.oracle_ref(r, iters=3)["E"])
     E = sc.oracle_ref(r)["E"]
     nnz = sc.nnz_share(E)
     compact, dense = sc.tile_shares(E)
-    print("r=%d nnz3=%.4f nnz10=%.4f compact=%.3f dense=%.3f" % (r, nnz3, nnz, compact, dense))
+    print("r=%s nnz3=%.4f nnz10=%.4f compact=%.3f dense=%.3f" % (r, nnz3, nnz, compact, dense))
     assert nnz3 >= sc.NNZ3_MIN
     assert sc.NNZ_BAND[0] <= nnz <= sc.NNZ_BAND[1]
     assert compact >= sc.TILE_SHARE_MIN and dense >= sc.TILE_SHARE_MIN
 
 
-@pytest.mark.parametrize("r", sc.RANKS)
+@pytest.mark.parametrize("r", CASES)
 def test_fp64_oracle_and_c_restatement_agree(r):
     a, b = sc.oracle_ref(r), sc.c_ref(r, False)
     assert a["k"] == b["k"] == sc.ITERS
@@ -51,11 +63,11 @@ def test_fp64_oracle_and_c_restatement_agree(r):
                       orc.triple_product(a["A"], a["B"], a["C"]))}
     for key in ("O", "E", "A", "B", "C", "errHist"):
         worst[key] = rel(b[key], a[key])
-    print("r=%d" % r, {k: "%.1e" % v for k, v in worst.items()})
+    print("r=%s" % r, {k: "%.1e" % v for k, v in worst.items()})
     assert max(worst.values()) <= 1e-11, worst
 
 
-@pytest.mark.parametrize("r", sc.RANKS)
+@pytest.mark.parametrize("r", CASES)
 def test_fp32_restatement_is_stable_under_input_rounding(r):
     mod, lib = sc.cref_lib()
     c = sc.e_active_case(r, np.float32)
@@ -64,15 +76,15 @@ def test_fp32_restatement_is_stable_under_input_rounding(r):
     assert np.any(base["E"])
     worst = 0.0
     for seed in (1, 2, 3):
-        rng = np.random.default_rng(1000 * r + seed)
+        rng = np.random.default_rng(1000 * (0 if r == sc.TALL else r) + seed)
         D = sc.perturbed(c["D"], U32, rng)
         A0 = sc.perturbed(c["A0"], U32, rng)
-        p = mod.admm(lib, D, r, c["opts"], A0, c["B0"], c["C0"])
+        p = mod.admm(lib, D, c["r"], c["opts"], A0, c["B0"], c["C0"])
         assert p[6] == base["k"]
         worst = max(worst, rel(orc.triple_product(p[0], p[1], p[2]), L0),
                     rel(p[3].astype(np.float64), base["O"].astype(np.float64)),
                     rel(p[5].astype(np.float64), base["E"].astype(np.float64)))
-    print("r=%d fp32 perturbation response %.2e" % (r, worst))
+    print("r=%s fp32 perturbation response %.2e" % (r, worst))
     assert worst <= 4e-6
 
 

@@ -118,15 +118,7 @@ void AlsSession::init(const ShardInputs& in, const NcvxParams* ncvx, hipStream_t
     // tensor in every iteration, before K2 reads it)
     if (!masked_) launch_tm_to_tx(g_, X_.p, XT_.p, st_);
 
-    std::vector<double> Ah, AhT, Bh, Ch, ChT;
-    pack_A(g_, in.A0, Ah, AhT);
-    pack_B(g_, in.B0, Bh);
-    pack_C(g_, in.C0, Ch, ChT);
-    TRITD_HIP(hipMemcpy(Ah_.p, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(AhT_.p, AhT.data(), AhT.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(Bh_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(Ch_.p, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(ChT_.p, ChT.data(), ChT.size() * sizeof(double), hipMemcpyHostToDevice));
+    upload_factors(g_, in.A0, in.B0, in.C0, Ah_.p, AhT_.p, Bh_.p, Ch_.p, ChT_.p);
     if (holdout_) val_.seed(Ah_.p, Bh_.p, Ch_.p);
 
     // Xnorm = norm(X(:))  (:6)

@@ -121,9 +121,9 @@ Session::Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_c
     if (!f32_) g_.tsplit = k5_tsplit(g_);
     // Schedules: one GPU without a group stream runs the
     // single-stream fused iteration (fp64 CP, RP <= 64) or else the
-    // overlapped one (side-stream Grams and solves); with a communicator the
-    // fused iteration with its two all-reduces, or the sharded side-stream
-    // one; device groups sharing a stream run the phase-serial order.
+    // side-stream one (Grams and solves on a second stream); with a
+    // communicator the same two with their all-reduces; device groups
+    // sharing a stream run the phase-serial order.
     overlap_ = (comm == nullptr) && (shared_stream == nullptr);
     dy_ = !f32_;  // derived Y_O (k_admm.hip): every fp64 session
     {
@@ -131,8 +131,7 @@ Session::Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_c
         de_mode_ = de ? std::atoi(de) : -1;
         // TRITD_SHOV=0: a communicator session runs the phase-serial order
         const char* sh = std::getenv("TRITD_SHOV");
-        shov_ = comm != nullptr && comm->active() && shared_stream == nullptr &&
-                !(sh && std::atoi(sh) == 0);
+        shov_ = sharded() && shared_stream == nullptr && !(sh && std::atoi(sh) == 0);
     }
     create_streams(shared_stream);
     if (overlap_ || shov_) {
@@ -246,7 +245,7 @@ Session::Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_c
         for (DBuf* b : {&GqA_, &GqB_, &GqC_}) b->alloc((size_t)g_.RP * g_.RP);
     }
     k5tail_ = k5n();
-    if (comm_ && comm_->active()) agree_counts();
+    if (sharded()) agree_counts();
     // + the tail for K5's norm partials (holdout: and the two score sums behind it)
     red1_.alloc(red1_count() + 2 * (size_t)k5tail_ + 2);
     red2_.alloc(red2_count());
@@ -290,7 +289,8 @@ Session::Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_c
         if (observed || holdout)
             pack_mask(observed, ldD, (flags & TRITD_SESSION_D_ON_DEVICE) != 0, holdout);
     }
-    upload_factors(in.A0, in.B0, in.C0);
+    upload_factors(g_, in.A0, in.B0, in.C0, Ah_.p, AhT_.p, Bh_.p, Ch_.p, ChT_.p,
+                   f32_ ? ChF_.f() : nullptr);
     if (holdout_) val_.seed(Ah_.p, Bh_.p, Ch_.p);
 
     // normD = norm(D(:))  (:28)
@@ -316,11 +316,10 @@ Session::Session(int device, const ShardInputs& in, const tritd_opts& o, tritd_c
     // T of iteration 1 (:33) and W = T x3 C0 for update_A/update_B
     if (o_.maxIter > 0) launch_k5_any(1, /*prologue=*/true);
     if (fused_) {
-        solve(0, BtB_.p, CtC_.p, o_.lambda2, GinvA_.p, st_);  // solve A of iteration 1
+        solve(0, st_);  // solve A of iteration 1
     } else if (overlap_ || shov_) {  // solve A of iteration 1 (needs the initial B^TB, C^TC)
-        TRITD_HIP(hipEventRecord(evCtC_, st_));
-        TRITD_HIP(hipStreamWaitEvent(side_, evCtC_, 0));
-        solve(0, BtB_.p, CtC_.p, o_.lambda2, GinvA_.p, side_);
+        side_after_main(evCtC_);
+        solve(0, side_);
         TRITD_HIP(hipEventRecord(evSA_, side_));
         TRITD_HIP(hipStreamSynchronize(side_));
     }
@@ -347,6 +346,13 @@ void Session::create_streams(hipStream_t shared_stream) {
         TRITD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
         TRITD_HIP(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, hi));
     }
+}
+
+// the side stream's next kernel runs behind everything enqueued on the main
+// stream so far
+void Session::side_after_main(hipEvent_t e) {
+    TRITD_HIP(hipEventRecord(e, st_));
+    TRITD_HIP(hipStreamWaitEvent(side_, e, 0));
 }
 
 Session::~Session() {
@@ -404,20 +410,21 @@ void Session::pack_mask(const uint8_t* observed, int64_t ldD, bool on_device,
     obs_count_d_ = (double)obs_count_;
 }
 
-void Session::upload_factors(const double* A0, const double* B0, const double* C0) {
+void upload_factors(const Geom& g, const double* A0, const double* B0, const double* C0, double* dAh,
+                    double* dAhT, double* dBh, double* dCh, double* dChT, float* dChF) {
     std::vector<double> Ah, AhT, Bh, Ch, ChT;
-    pack_A(g_, A0, Ah, AhT);
-    pack_B(g_, B0, Bh);
-    pack_C(g_, C0, Ch, ChT);
-    TRITD_HIP(hipMemcpy(Ah_.p, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(AhT_.p, AhT.data(), AhT.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(Bh_.p, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(Ch_.p, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
-    TRITD_HIP(hipMemcpy(ChT_.p, ChT.data(), ChT.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (f32_) {
+    pack_A(g, A0, Ah, AhT);
+    pack_B(g, B0, Bh);
+    pack_C(g, C0, Ch, ChT);
+    TRITD_HIP(hipMemcpy(dAh, Ah.data(), Ah.size() * sizeof(double), hipMemcpyHostToDevice));
+    TRITD_HIP(hipMemcpy(dAhT, AhT.data(), AhT.size() * sizeof(double), hipMemcpyHostToDevice));
+    TRITD_HIP(hipMemcpy(dBh, Bh.data(), Bh.size() * sizeof(double), hipMemcpyHostToDevice));
+    TRITD_HIP(hipMemcpy(dCh, Ch.data(), Ch.size() * sizeof(double), hipMemcpyHostToDevice));
+    TRITD_HIP(hipMemcpy(dChT, ChT.data(), ChT.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (dChF) {
         std::vector<float> cf(Ch.size());
         for (size_t e = 0; e < Ch.size(); ++e) cf[e] = (float)Ch[e];
-        TRITD_HIP(hipMemcpy(ChF_.p, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice));
+        TRITD_HIP(hipMemcpy(dChF, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice));
     }
 }
 
@@ -457,29 +464,32 @@ void Session::do_m1() {
     else if (f32_)  // (its finish rides in M2: do_m2)
         launch_m1_32(g_, Wk_.f(), Bh_.p, M1_.f(), ctrl_, st_);
     else  // the previous K5's norm reduction and stop test in an extra workgroup (finish.h)
-        launch_m1(g_, Wk_.p, Bh_.p, M1_.p, ctrl_, st_, take_finish());
+        launch_m1(g_, Wk_.p, Bh_.p, M1_.p, ctrl_, st_, take_finish(false));
 }
 
-// The pending norm reduction + stop test of the previous iteration (single
-// GPU: K5's own partials), for an extra workgroup of the next M1 / M2
-FinishArgs Session::take_finish() {
+// The pending norm reduction + stop test of the previous iteration, for the
+// launch that carries it: on one GPU (after_allreduce = false) an extra
+// workgroup of the next M1 / M2 over K5's own partials; with a communicator
+// (true) update_B's solve, behind the all-reduce that summed red1_'s tail
+// (cleared once consumed).  on = 0: nothing pends for that carrier.
+FinishArgs Session::take_finish(bool after_allreduce) {
     FinishArgs f;
-    if (norms_pending_ && !(comm_ && comm_->active())) {
-        f.p = k5part_.p; f.n = k5n(); f.normD = normD_; f.k = pend_k_; f.tol = o_.tol;
+    if (norms_pending_ && after_allreduce == sharded()) {
+        f.p = norm_parts(); f.n = norm_pairs(); f.normD = normD_; f.k = pend_k_; f.tol = o_.tol;
         f.errHist = errHist_.p; f.errL = errL_.p; f.errO = errO_.p; f.ctrl = ctrl_;
-        f.single = (int)f32_; f.on = 1;
+        f.single = (int)f32_; f.clear = (int)after_allreduce; f.on = 1;
         norms_pending_ = false;
     }
     return f;
 }
 
-void Session::do_m2(double* M2) {
+void Session::do_m2() {
     if (qi_)
-        launch_m2_qi(g_, g_.r, Wk_.p, AhT_.p, M2, ctrl_, st_);
+        launch_m2_qi(g_, g_.r, Wk_.p, AhT_.p, m2(), ctrl_, st_);
     else if (f32_)
-        launch_m2_32(g_, Wk_.f(), AhT_.p, M2, ctrl_, st_, take_finish());
+        launch_m2_32(g_, Wk_.f(), AhT_.p, m2(), ctrl_, st_, take_finish(false));
     else
-        launch_m2(g_, Wk_.p, AhT_.p, M2, ctrl_, st_);
+        launch_m2(g_, Wk_.p, AhT_.p, m2(), ctrl_, st_);
 }
 
 void Session::do_m3() {
@@ -497,59 +507,87 @@ void Session::do_m3_qi() {
     launch_m3(g_, T_.p, H_.p, ones_.p, m3part_.p, red2_.p, ctrl_, st_, g_.n1p * g_.RP, 0);
 }
 
-void Session::solve(int mode, const double* P, const double* Q, double alpha, double* out,
-                    hipStream_t s, const FinishArgs* fin) {
+// The operands of each solve, stated once: update_A (:73-81) inverts
+// B^TB o C^TC + lambda2 I, update_B (:83-88) A^TA o C^TC + lambda2 I,
+// update_C A^TA o B^TB + 1e-9 I (:93 ridge), each into its own Ginv slot.
+SideSolve Session::side_solve(int mode, const Update* gram) const {
+    SideSolve s;
+    s.P = mode == 0 ? BtB_.p : ata();
+    s.Q = mode == 2 ? BtB_.p : CtC_.p;
+    s.alpha = mode == 2 ? 1e-9 : o_.lambda2;
+    s.Ginv = (mode == 0 ? GinvA_ : mode == 1 ? GinvB_ : GinvC_).p;
+    s.flags = ctrl_ + 2;
+    s.R = g_.R;
+    s.on = 1;
+    if (gram) {  // the side workgroup first forms that operand itself, as Y^T Y into G
+        s.gram_src = gram->Y;
+        s.gram_rows = gram->rows;
+        s.gram_to = gram->G;
+        s.gram_which = gram->G == s.P ? 0 : 1;
+    }
+    return s;
+}
+
+void Session::solve(int mode, hipStream_t s, const FinishArgs* fin) {
+    const SideSolve o = side_solve(mode);
     if (!qi_) {
-        launch_solve(g_.RP, g_.R, P, Q, alpha, out, ctrl_ + 2, ctrl_, s, fin);
+        launch_solve(g_.RP, g_.R, o.P, o.Q, o.alpha, o.Ginv, o.flags, ctrl_, s, fin);
     } else {
         if (fin) throw Error(TRITD_ERR_ARG, "solve with a finish: CP model only");
         double* G = (mode == 0 ? GqA_ : mode == 1 ? GqB_ : GqC_).p;
-        launch_qi_gram(g_.RP, g_.r, mode, P, Q, G, ctrl_, s);
-        launch_solve(g_.RP, g_.R, G, ones_.p, alpha, out, ctrl_ + 2, ctrl_, s);
+        launch_qi_gram(g_.RP, g_.r, mode, o.P, o.Q, G, ctrl_, s);
+        launch_solve(g_.RP, g_.R, G, ones_.p, o.alpha, o.Ginv, o.flags, ctrl_, s);
     }
     // the generic apply's pinv fallback, on the solve's stream (a side-stream
     // solve then hands over a finished Ginv: one launch fewer on the main one).
     // Not for mode 0: solve A of iteration k+1 runs beside K5 of k, before k's
     // stop test, and a fallback there could raise TRITD_FLAG_PINV_TOL for an
     // update_A that MATLAB never performs when the loop stops at k (ADVICE
-    // r5); apply A runs the fallback itself, after the stop test (do_apply_A)
-    if (gen_apply() && mode != 0) launch_pinv_fix(g_.RP, out, ctrl_, ctrl_ + 2, s);
+    // r5); apply A runs the fallback itself, after the stop test (Update::fix)
+    if (gen_apply() && mode != 0) launch_pinv_fix(g_.RP, o.Ginv, ctrl_, ctrl_ + 2, s);
+}
+
+// The operands of update_A / _B / _C (mode 0 / 1 / 2).  A^ follows the parity
+// buffers (set_ah), so update_A is described when it is issued, not once.
+Update Session::upd(int mode) const {
+    Update u;
+    if (mode == 0) {  // A^ = M1 * GinvA (M1 is single on the fp32 path)
+        if (f32_)
+            u.Mf = M1_.f();
+        else
+            u.M = M1_.p;
+        u.rows = u.ldT = g_.n1p;
+        u.Ginv = GinvA_.p;
+        u.Y = Ah_.p;
+        u.YT = AhT_.p;
+        u.G = ata();
+        u.fix = true;  // the pinv fallback of solve A runs in the apply, after the stop test
+    } else if (mode == 1) {  // B^ = M2 * GinvB
+        u.M = m2();
+        u.rows = g_.n2;
+        u.Ginv = GinvB_.p;
+        u.Y = Bh_.p;
+        u.G = BtB_.p;
+    } else {  // C^ = M3 * GinvC
+        u.M = red2_.p;
+        u.rows = u.ldT = g_.n3p;
+        u.Ginv = GinvC_.p;
+        u.Y = Ch_.p;
+        u.YT = ChT_.p;
+        u.YF = f32_ ? ChF_.f() : nullptr;
+        u.G = CtC_.p;
+    }
+    return u;
 }
 
 // (X*F')*pinv(G): fp64 path through the MFMA apply (RP <= 64); fp32
 // path single in, single-rounded out (MATLAB single * double = single)
-void Session::do_apply_A(double* Ginv) {
-    // (fix = true: the pinv fallback of solve A runs here, after the stop test)
-    if (f32_)
-        launch_apply_gen(g_.RP, nullptr, M1_.f(), g_.n1p, Ginv, Ah_.p, AhT_.p, g_.n1p, nullptr,
-                         true, ctrl_, ctrl_ + 2, st_, true);
-    else if (g_.RP > 64)  // fp64 r = 9..16
-        launch_apply_gen(g_.RP, M1_.p, nullptr, g_.n1p, Ginv, Ah_.p, AhT_.p, g_.n1p, nullptr,
-                         false, ctrl_, ctrl_ + 2, st_, true);
+void Session::apply(const Update& u) {
+    if (gen_apply())  // fp32, or fp64 r = 9..16
+        launch_apply_gen(g_.RP, u.M, u.Mf, u.rows, u.Ginv, u.Y, u.YT, u.ldT, u.YF, /*round32=*/f32_,
+                         ctrl_, ctrl_ + 2, st_, u.fix);
     else
-        launch_apply(g_.RP, M1_.p, g_.n1p, Ginv, Ah_.p, AhT_.p, g_.n1p, ctrl_, ctrl_ + 2, st_);
-}
-
-void Session::do_apply_B(const double* M2, double* Ginv) {
-    if (f32_)
-        launch_apply_gen(g_.RP, M2, nullptr, g_.n2, Ginv, Bh_.p, nullptr, 0, nullptr, true, ctrl_, ctrl_ + 2,
-                         st_, false);
-    else if (g_.RP > 64)  // fp64 r = 9..16
-        launch_apply_gen(g_.RP, M2, nullptr, g_.n2, Ginv, Bh_.p, nullptr, 0, nullptr, false, ctrl_, ctrl_ + 2,
-                         st_, false);
-    else
-        launch_apply(g_.RP, M2, g_.n2, Ginv, Bh_.p, nullptr, 0, ctrl_, ctrl_ + 2, st_);
-}
-
-void Session::do_apply_C(double* Ginv) {
-    if (f32_)
-        launch_apply_gen(g_.RP, red2_.p, nullptr, g_.n3p, Ginv, Ch_.p, ChT_.p, g_.n3p, ChF_.f(),
-                         true, ctrl_, ctrl_ + 2, st_, false);
-    else if (g_.RP > 64)  // fp64 r = 9..16
-        launch_apply_gen(g_.RP, red2_.p, nullptr, g_.n3p, Ginv, Ch_.p, ChT_.p, g_.n3p, nullptr,
-                         false, ctrl_, ctrl_ + 2, st_, false);
-    else
-        launch_apply(g_.RP, red2_.p, g_.n3p, Ginv, Ch_.p, ChT_.p, g_.n3p, ctrl_, ctrl_ + 2, st_);
+        launch_apply(g_.RP, u.M, u.rows, u.Ginv, u.Y, u.YT, u.ldT, ctrl_, ctrl_ + 2, st_);
 }
 
 // apply + Gram of one factor (update_A/B/C, :77-81,86-88,93-95): one launch
@@ -566,46 +604,17 @@ bool Session::small_ag(int64_t rows) const {
 // K2 / K5 of a 64-row shard it doubled both, round 5, while at config 4 it
 // moved nothing beyond box noise: profiles/round5/shard8_deferred_grams.txt).
 // Returns whether the Gram was left to the side solve.
-bool Session::apply_gram_A(double* AtA, bool defer) {
-    if (defer && small_ag(g_.n1p)) {
-        do_apply_A(GinvA_.p);
-        return true;
-    }
-    if (small_ag(g_.n1p)) {
-        launch_apply_gram(g_.RP, M1_.p, g_.n1p, GinvA_.p, Ah_.p, AhT_.p, g_.n1p, AtA, ctrl_, ctrl_ + 2, st_);
+bool Session::apply_gram(const Update& u, bool defer) {
+    const bool small = small_ag(u.rows);
+    if (small && !defer) {
+        launch_apply_gram(g_.RP, u.M, u.rows, u.Ginv, u.Y, u.YT, u.ldT, u.G, ctrl_, ctrl_ + 2, st_);
         return false;
     }
-    do_apply_A(GinvA_.p);
-    launch_gram(g_.RP, Ah_.p, g_.n1p, AtA, ctrl_, st_);
-    return false;
-}
-
-bool Session::apply_gram_B(const double* M2, bool defer) {
-    if (defer && small_ag(g_.n2)) {  // the Gram rides beside K2 (side solve C)
-        do_apply_B(M2, GinvB_.p);
-        return true;
-    }
-    if (small_ag(g_.n2)) {
-        launch_apply_gram(g_.RP, M2, g_.n2, GinvB_.p, Bh_.p, nullptr, 0, BtB_.p, ctrl_, ctrl_ + 2, st_);
-        return false;
-    }
-    do_apply_B(M2, GinvB_.p);
-    launch_gram(g_.RP, Bh_.p, g_.n2, BtB_.p, ctrl_, st_);
-    return false;
-}
-
-bool Session::apply_gram_C(bool defer) {
-    if (defer && small_ag(g_.n3p)) {  // the Gram rides beside K5 (side solve A of k+1)
-        do_apply_C(GinvC_.p);
-        return true;
-    }
-    if (small_ag(g_.n3p)) {
-        launch_apply_gram(g_.RP, red2_.p, g_.n3p, GinvC_.p, Ch_.p, ChT_.p, g_.n3p, CtC_.p, ctrl_, ctrl_ + 2,
-                          st_);
-        return false;
-    }
-    do_apply_C(GinvC_.p);
-    launch_gram(g_.RP, Ch_.p, g_.n3p, CtC_.p, ctrl_, st_);
+    apply(u);
+    // (deferred: A's Gram rides beside M2 in side solve B, B's beside K2 in
+    // side solve C, C's beside K5 in side solve A of k+1)
+    if (small) return true;
+    launch_gram(g_.RP, u.Y, u.rows, u.G, ctrl_, st_);
     return false;
 }
 
@@ -613,9 +622,7 @@ bool Session::apply_gram_C(bool defer) {
 // only (with a communicator A^TA is all-reduced with M2 before update_B's
 // solve: it is formed by a gram-only side job of M2 instead), B's and C's in
 // either case (replicated factors)
-bool Session::side_gram_ok() const {
-    return side_gram_bc_ok() && !(comm_ && comm_->active());
-}
+bool Session::side_gram_ok() const { return side_gram_bc_ok() && !sharded(); }
 
 bool Session::side_gram_bc_ok() const { return !f32_ && !qi_ && g_.RP <= 64; }
 
@@ -623,18 +630,10 @@ bool Session::side_gram_bc_ok() const { return !f32_ && !qi_ && g_.RP <= 64; }
 // 64 rows (16 K-steps of the side Gram, which then ends inside M2's time;
 // its load round trips make 128+ rows outlast M2)
 bool Session::gram_a_in_m2() const {
-    return side_gram_bc_ok() && comm_ && comm_->active() && g_.n1p <= 64;
+    return side_gram_bc_ok() && sharded() && g_.n1p <= 64;
 }
 
-// side solve `s` first forms operand `which` (0 = P, 1 = Q) as X^T X into `to`
-static void with_gram(SideSolve& s, const double* X, int64_t rows, double* to, int which) {
-    s.gram_src = X;
-    s.gram_rows = rows;
-    s.gram_to = to;
-    s.gram_which = which;
-}
-
-void Session::launch_k5_any(int k, bool prologue) {
+void Session::launch_k5_any(int k, bool prologue, double* partial, const SideSolve& side) {
     if (f32_) {
         K5Args32 a{};
         a.D = D_.f(); a.O = O_.f(); a.E = E_.f(); a.CE = CE_.f(); a.YL = YL_.f(); a.YO = YO_.f();
@@ -655,7 +654,7 @@ void Session::launch_k5_any(int k, bool prologue) {
     a.E = e_buf(k - 1); a.CE = ce_buf(k - 1);
     a.Ep = e_buf(k); a.CEp = ce_buf(k);
     a.Ah = Ah_.p; a.Bh = Bh_.p; a.Ch = Ch_.p; a.ChT = ChT_.p;
-    a.partial = (k5part_to_ && !prologue) ? k5part_to_ : k5part_.p;
+    a.partial = partial ? partial : k5part_.p;
     a.ahj = 0; a.bhj = g_.RP;
     if (qi_) {  // L = H Ch^T (H built before K2 of this iteration)
         a.Ah = H_.p; a.Bh = ones_.p;
@@ -667,10 +666,7 @@ void Session::launch_k5_any(int k, bool prologue) {
     a.stop = ctrl_;
     a.dense_tiles = dense_tiles();
     a.M = mask_words();
-    if (!prologue) {
-        a.side = k5side_;
-        k5side_ = SideSolve{};
-    }
+    a.side = side;
     launch_k5(g_, a, prologue, st_, de_ && !prologue);
 }
 
@@ -785,7 +781,7 @@ void comm_allreduce(tritd_comm* c, double* buf, int64_t count, bool max, hipStre
 }
 
 void Session::allreduce(double* buf, int64_t count) {
-    if (!comm_ || !comm_->active()) return;
+    if (!sharded()) return;
     const int a = ar_in_iter_++;
     if (a < EV_AR) mark(6 + 2 * a);
     comm_allreduce(comm_, buf, count, false, st_);
@@ -843,47 +839,34 @@ void Session::set_ah(int k) {
 
 void Session::flush_norms() {
     if (!norms_pending_) return;
-    if (!(comm_ && comm_->active())) {  // single GPU: K5's own partials
-        launch_reduce_finish(k5part_.p, k5n(), normD_, pend_k_, o_.tol, errHist_.p, errL_.p, errO_.p,
-                             ctrl_, f32_, st_);
-        norms_pending_ = false;
-        return;
-    }
-    double* parts = red1_.p + red1_count();
-    allreduce(parts, 2 * (int64_t)k5tail_);
-    launch_reduce_finish(parts, k5tail_, normD_, pend_k_, o_.tol, errHist_.p, errL_.p, errO_.p,
-                         ctrl_, f32_, st_, /*clear=*/true);
+    // (single GPU: K5's own partials; a communicator's tail is summed first
+    // and cleared once consumed)
+    if (sharded()) allreduce(norm_parts(), 2 * (int64_t)norm_pairs());
+    launch_reduce_finish(norm_parts(), norm_pairs(), normD_, pend_k_, o_.tol, errHist_.p, errL_.p,
+                         errO_.p, ctrl_, f32_, st_, /*clear=*/sharded());
     norms_pending_ = false;
 }
 
 void Session::phaseA(int k) {
     (void)k;
-    const int RP = g_.RP;
-    double* M2 = red1_.p;
-    double* AtA = red1_.p + g_.n2 * RP;
     do_m1();
-    solve(0, BtB_.p, CtC_.p, o_.lambda2, GinvA_.p, st_);
-    apply_gram_A(AtA);
-    do_m2(M2);
+    solve(0, st_);
+    apply_gram(upd(0));
+    do_m2();
 }
 
 void Session::phaseB(int k) {
     (void)k;
-    const int RP = g_.RP;
-    const double* M2 = red1_.p;
-    const double* AtA = red1_.p + g_.n2 * RP;
-    solve(1, AtA, CtC_.p, o_.lambda2, GinvB_.p, st_);
-    apply_gram_B(M2);
+    solve(1, st_);
+    apply_gram(upd(1));
     mark(1);
     do_m3();
     mark(2);
 }
 
 void Session::phaseC(int k) {
-    const int RP = g_.RP;
-    const double* AtA = red1_.p + g_.n2 * RP;
-    solve(2, AtA, BtB_.p, 1e-9, GinvC_.p, st_);  // :93 ridge
-    apply_gram_C();
+    solve(2, st_);
+    apply_gram(upd(2));
     launch_k5_full(k, /*fused_finish=*/false);
     if (holdout_) holdout_score(red3_.p + 2);
 }
@@ -1029,67 +1012,86 @@ void Session::launch_k5_full(int k, bool fused_finish) {
         launch_reduce_pairs(k5part_.p, k5n(), red3_.p, ctrl_, st_);
 }
 
-// Single-GPU iteration.  Same kernels and data flow as phases A-D, but each
-// R x R solve runs on the side stream as soon as its Grams exist:
-//   solve B (A^TA, C^TC) || M2        solve C (A^TA, B^TB) || M3
-//   solve A of k+1 (B^TB, C^TC) || K5
-// Every buffer a side kernel reads is next written on the main stream only
-// after an event the side stream records behind that kernel.
-void Session::iterate_overlapped(int k) {
+// K5 of iteration k with its norm reduction and stop test left pending.  One
+// GPU: they ride in the next M1 (do_m1; fp32: M2, do_m2).  Communicator: the
+// norm partials stay per workgroup in red1_'s tail and are all-reduced with
+// the next iteration's M2 | A^TA.  Or flush_norms when the loop ends first.
+void Session::launch_k5_pending(int k, const SideSolve& side) {
+    mark(3);
+    launch_k5_any(k, /*prologue=*/false, norm_parts(), side);
+    mark(4);
+    norms_pending_ = true;
+    pend_k_ = k;
+}
+
+// Side-stream iteration.  Same kernels and data flow as phases A-D, but the
+// replicated Grams and the R x R solves run on the side stream as soon as
+// their operands exist:
+//   main: M1 -> apply A -> Gram A -> M2 -> AR(M2 | A^TA) -> apply B -> K2
+//         -> AR(M3) -> apply C -> K5 -> the ending
+//   side: Gram B -> solve C (|| K2 + its AR) | Gram C -> solve A(k+1) (|| K5)
+// Solve B goes where its A^TA is complete: on one GPU ahead of M2 (main
+// stream; RP >= 128 side stream, || M2), with a communicator behind the
+// all-reduce.  The all-reduces are those of one process per GPU (SURVEY.md
+// §8e); without a communicator they vanish.  The ending: one GPU leaves the
+// norms pending (Qi: the fused finish; holdout: holdout_tail), a communicator
+// reduces them, all-reduces red3 and runs phase D.
+// Hazard rule: every buffer a side kernel reads is next written on the main
+// stream only after an event the side stream records behind that kernel.
+void Session::iterate_side(int k) {
     const int RP = g_.RP;
-    double* M2 = red1_.p;
-    double* AtA = red1_.p + g_.n2 * RP;
-    // main: M1 -> apply A -> Gram A -> solve B -> M2 -> apply B -> K2 -> apply C -> K5 -> finish
-    // side: Gram B -> solve C (|| K2) | Gram C -> solve A(k+1) (|| K5)
+    const Update uA = upd(0), uB = upd(1), uC = upd(2);
+    const bool sh = sharded();
+    do_m1();
+    TRITD_HIP(hipStreamWaitEvent(st_, evSA_, 0));
+    apply(uA);
+    launch_gram(RP, uA.Y, uA.rows, uA.G, ctrl_, st_);
     // Gram A^TA and solve B are on the critical path (M2 beside them is only
     // ~20 us): on the main stream they cost their own time, on the side stream
     // that plus two cross-stream waits (each widens a kernel boundary by ~6 us)
-    do_m1();
-    TRITD_HIP(hipStreamWaitEvent(st_, evSA_, 0));
-    do_apply_A(GinvA_.p);
-    launch_gram(RP, Ah_.p, g_.n1p, AtA, ctrl_, st_);
-    if (RP >= 128) {
+    const bool side_b = !sh && RP >= 128;
+    if (side_b) {
         // padded ranks 128 / 256 (config 5): solve B (~0.15 ms, k_solve_mw)
         // on the high-priority side stream, issued before M2 (~0.65 ms there)
         // so that its workgroups are dispatched first and run beside it
-        TRITD_HIP(hipEventRecord(evAtA_, st_));
-        TRITD_HIP(hipStreamWaitEvent(side_, evAtA_, 0));
-        solve(1, AtA, CtC_.p, o_.lambda2, GinvB_.p, side_);
+        side_after_main(evAtA_);
+        solve(1, side_);
         TRITD_HIP(hipEventRecord(evSB_, side_));
-        do_m2(M2);
-        TRITD_HIP(hipStreamWaitEvent(st_, evSB_, 0));
-    } else {
-        solve(1, AtA, CtC_.p, o_.lambda2, GinvB_.p, st_);
-        do_m2(M2);
+    } else if (!sh) {
+        solve(1, st_);
     }
-    do_apply_B(M2, GinvB_.p);
-    TRITD_HIP(hipEventRecord(evBtB_, st_));
-    TRITD_HIP(hipStreamWaitEvent(side_, evBtB_, 0));
-    launch_gram(RP, Bh_.p, g_.n2, BtB_.p, ctrl_, side_, true);
-    solve(2, AtA, BtB_.p, 1e-9, GinvC_.p, side_);  // :93 ridge
+    do_m2();
+    if (side_b) TRITD_HIP(hipStreamWaitEvent(st_, evSB_, 0));
+    if (sh) {  // the all-reduce of M2 + A^TA gates solve B, which stays on the critical path
+        allreduce(red1_.p, red1_count());
+        solve(1, st_);
+    }
+    apply(uB);
+    side_after_main(evBtB_);
+    launch_gram(RP, uB.Y, uB.rows, uB.G, ctrl_, side_, true);
+    solve(2, side_);
     TRITD_HIP(hipEventRecord(evSC_, side_));
     mark(1);
     do_m3();
     mark(2);
+    allreduce(red2_.p, red2_count());
     TRITD_HIP(hipStreamWaitEvent(st_, evSC_, 0));
-    do_apply_C(GinvC_.p);
-    TRITD_HIP(hipEventRecord(evCtC_, st_));
-    TRITD_HIP(hipStreamWaitEvent(side_, evCtC_, 0));
-    launch_gram(RP, Ch_.p, g_.n3p, CtC_.p, ctrl_, side_, true);
-    solve(0, BtB_.p, CtC_.p, o_.lambda2, GinvA_.p, side_);
+    apply(uC);
+    side_after_main(evCtC_);
+    launch_gram(RP, uC.Y, uC.rows, uC.G, ctrl_, side_, true);
+    solve(0, side_);
     TRITD_HIP(hipEventRecord(evSA_, side_));
-    if (qi_) {
+    if (sh) {
+        launch_k5_full(k, /*fused_finish=*/false);
+        if (holdout_) holdout_score(red3_.p + 2);
+        allreduce(red3_.p, red3_count());
+        phaseD(k);
+    } else if (qi_) {
         launch_k5_full(k, /*fused_finish=*/true);
-        return;
+    } else {
+        launch_k5_pending(k);
+        if (holdout_) holdout_tail(k);
     }
-    // the norm reduction and stop test of k ride in the next M1 (do_m1; fp32:
-    // M2, do_m2), or flush_norms when the loop ends first
-    mark(3);
-    launch_k5_any(k, /*prologue=*/false);
-    mark(4);
-    norms_pending_ = true;
-    pend_k_ = k;
-    if (holdout_) holdout_tail(k);
 }
 
 // Single-stream iteration (fused_): every kernel on the main stream in
@@ -1099,128 +1101,47 @@ void Session::iterate_overlapped(int k) {
 // One process per GPU: M2 -> AR(M2 | A^TA) -> solve B (k_solve_ns, main),
 // AR(M3) after K2, AR(norms) after K5.
 void Session::iterate_fused(int k) {
-    const int RP = g_.RP;
-    double* M2 = red1_.p;
-    double* AtA = red1_.p + g_.n2 * RP;
+    const Update uA = upd(0), uB = upd(1), uC = upd(2);
     std::unique_ptr<Range> ph(new Range("update_A (:73-81)"));
     const bool defer = side_gram_ok(), defer_bc = side_gram_bc_ok();
     const bool ga_m2 = gram_a_in_m2();
     do_m1();
-    const bool gA = ga_m2 ? (do_apply_A(GinvA_.p), false) : apply_gram_A(AtA, defer);
+    const bool gA = ga_m2 ? (apply(uA), false) : apply_gram(uA, defer);
     ph.reset(new Range("update_B (:83-88)"));
-    if (comm_ && comm_->active()) {
+    if (sharded()) {
         if (ga_m2) {  // A^T A beside M2, for the all-reduce below
-            SideSolve sg;
-            sg.on = 1;
-            sg.solve = 0;
-            sg.R = g_.R;
-            with_gram(sg, Ah_.p, g_.n1p, AtA, 0);
-            launch_m2(g_, Wk_.p, AhT_.p, M2, ctrl_, st_, sg);
+            SideSolve sg = side_solve(1, &uA);
+            sg.solve = 0;  // (the Gram only: the solve needs the all-reduced A^T A)
+            launch_m2(g_, Wk_.p, AhT_.p, m2(), ctrl_, st_, sg);
         } else {
-            do_m2(M2);
+            do_m2();
         }
         // M1 .. M2 above ran before the stop test of iteration k-1: they
         // write only scratch and this iteration's A^ parity buffer.  The
         // all-reduce carries K5(k-1)'s norm partials; the finish of k-1
         // follows it, and every kernel after that checks its stop flag.
-        const bool pend = norms_pending_;
-        allreduce(red1_.p, red1_count() + (pend ? 2 * (int64_t)k5tail_ : 0));
+        allreduce(red1_.p, red1_count() + (norms_pending_ ? 2 * (int64_t)k5tail_ : 0));
         // the finish of k-1 and update_B's solve in one launch (the finish
         // runs first; the apply of B after it sees its stop flag)
-        FinishArgs f;
-        if (pend) {
-            f.p = red1_.p + red1_count(); f.n = k5tail_; f.normD = normD_; f.k = pend_k_;
-            f.tol = o_.tol; f.errHist = errHist_.p; f.errL = errL_.p; f.errO = errO_.p;
-            f.ctrl = ctrl_; f.single = (int)f32_; f.clear = 1; f.on = 1;
-            norms_pending_ = false;
-        }
-        solve(1, AtA, CtC_.p, o_.lambda2, GinvB_.p, st_, pend ? &f : nullptr);
+        const FinishArgs f = take_finish(true);
+        solve(1, st_, f.on ? &f : nullptr);
     } else {
         // update_B's solve (A^TA of this iteration, C^TC) beside M2
-        SideSolve sb;
-        sb.P = AtA; sb.Q = CtC_.p; sb.alpha = o_.lambda2; sb.Ginv = GinvB_.p; sb.flags = ctrl_ + 2;
-        sb.R = g_.R; sb.on = 1;
-        if (gA) with_gram(sb, Ah_.p, g_.n1p, AtA, 0);
-        launch_m2(g_, Wk_.p, AhT_.p, M2, ctrl_, st_, sb);
+        launch_m2(g_, Wk_.p, AhT_.p, m2(), ctrl_, st_, side_solve(1, gA ? &uA : nullptr));
     }
-    const bool gB = apply_gram_B(M2, defer_bc);
+    const bool gB = apply_gram(uB, defer_bc);
     ph.reset(new Range("update_C (:90-95)"));
     mark(1);
-    SideSolve sc;  // update_C's solve (:93 ridge) beside K2
-    sc.P = AtA; sc.Q = BtB_.p; sc.alpha = 1e-9; sc.Ginv = GinvC_.p; sc.flags = ctrl_ + 2;
-    sc.R = g_.R; sc.on = 1;
-    if (gB) with_gram(sc, Bh_.p, g_.n2, BtB_.p, 1);
-    launch_m3(g_, T_.p, Ah_.p, Bh_.p, m3part_.p, red2_.p, ctrl_, st_, 0, -1, sc);
+    // update_C's solve (:93 ridge) beside K2
+    launch_m3(g_, T_.p, Ah_.p, Bh_.p, m3part_.p, red2_.p, ctrl_, st_, 0, -1,
+              side_solve(2, gB ? &uB : nullptr));
     mark(2);
     allreduce(red2_.p, red2_count());
-    const bool gC = apply_gram_C(defer_bc);
+    const bool gC = apply_gram(uC, defer_bc);
     // the next update_A's solve (B^TB, C^TC of this iteration) beside K5
     ph.reset(new Range("fused update K5 (:38-59, :33)"));
-    k5side_.P = BtB_.p; k5side_.Q = CtC_.p; k5side_.alpha = o_.lambda2; k5side_.Ginv = GinvA_.p;
-    k5side_.flags = ctrl_ + 2; k5side_.R = g_.R; k5side_.on = 1;
-    if (gC) with_gram(k5side_, Ch_.p, g_.n3p, CtC_.p, 1);
-    if (comm_ && comm_->active()) {
-        // the norm partials stay per workgroup in red1_'s tail: all-reduced
-        // with the next iteration's M2 | A^TA (or by flush_norms)
-        k5part_to_ = red1_.p + red1_count();
-        mark(3);
-        launch_k5_any(k, /*prologue=*/false);
-        mark(4);
-        k5part_to_ = nullptr;
-        norms_pending_ = true;
-        pend_k_ = k;
-    } else {
-        // the norm reduction and stop test of k ride in the next M1 (do_m1),
-        // or flush_norms when the loop ends first
-        mark(3);
-        launch_k5_any(k, /*prologue=*/false);
-        mark(4);
-        norms_pending_ = true;
-        pend_k_ = k;
-    }
+    launch_k5_pending(k, side_solve(0, gC ? &uC : nullptr));
     if (holdout_) holdout_tail(k);
-}
-
-// Sharded iteration (one process per GPU).  The all-reduce
-// of M2 + A^TA gates solve B, which stays on the critical path; the other two
-// solves and the two replicated Grams run on the side stream:
-//   main: M1 -> apply A -> Gram A -> M2 -> AR(M2, A^TA) -> solve B -> apply B
-//         -> M3 -> AR(M3) -> apply C -> K5 -> AR(norms) -> finish
-//   side: Gram B -> solve C (|| M3 + its AR) | Gram C -> solve A(k+1) (|| K5)
-// Hazards as in iterate_overlapped: every buffer a side kernel reads is next
-// written on the main stream only after an event recorded behind it.
-void Session::iterate_sharded(int k) {
-    const int RP = g_.RP;
-    double* M2 = red1_.p;
-    double* AtA = red1_.p + g_.n2 * RP;
-    do_m1();
-    TRITD_HIP(hipStreamWaitEvent(st_, evSA_, 0));
-    do_apply_A(GinvA_.p);
-    launch_gram(RP, Ah_.p, g_.n1p, AtA, ctrl_, st_);
-    do_m2(M2);
-    allreduce(red1_.p, red1_count());
-    solve(1, AtA, CtC_.p, o_.lambda2, GinvB_.p, st_);
-    do_apply_B(M2, GinvB_.p);
-    TRITD_HIP(hipEventRecord(evBtB_, st_));
-    TRITD_HIP(hipStreamWaitEvent(side_, evBtB_, 0));
-    launch_gram(RP, Bh_.p, g_.n2, BtB_.p, ctrl_, side_, true);
-    solve(2, AtA, BtB_.p, 1e-9, GinvC_.p, side_);  // :93 ridge
-    TRITD_HIP(hipEventRecord(evSC_, side_));
-    mark(1);
-    do_m3();
-    mark(2);
-    allreduce(red2_.p, red2_count());
-    TRITD_HIP(hipStreamWaitEvent(st_, evSC_, 0));
-    do_apply_C(GinvC_.p);
-    TRITD_HIP(hipEventRecord(evCtC_, st_));
-    TRITD_HIP(hipStreamWaitEvent(side_, evCtC_, 0));
-    launch_gram(RP, Ch_.p, g_.n3p, CtC_.p, ctrl_, side_, true);
-    solve(0, BtB_.p, CtC_.p, o_.lambda2, GinvA_.p, side_);
-    TRITD_HIP(hipEventRecord(evSA_, side_));
-    launch_k5_full(k, /*fused_finish=*/false);
-    if (holdout_) holdout_score(red3_.p + 2);
-    allreduce(red3_.p, red3_count());
-    phaseD(k);
 }
 
 // The score of a holdout iteration, after its K5: T holds L_k outside the fit
@@ -1239,26 +1160,22 @@ void Session::holdout_finish(int k, const double* ss, const double* hs) {
     val_.snapshot(Ah_.p, Bh_.p, Ch_.p, st_);
 }
 
-// The end of a holdout iteration on the fused and overlapped schedules: the
+// The end of a holdout iteration on the fused and side-stream schedules: the
 // norms do not pend for the next iteration's M1 / M2.  K5's partials are
 // reduced in flush_norms' order (k_reduce_pairs sums like reduce_finish_wg:
 // errHist keeps its bits); with a communicator the two score sums ride behind
 // the norm partials in red1_'s tail, in their all-reduce.
 void Session::holdout_tail(int k) {
-    if (!(comm_ && comm_->active())) {
-        holdout_score(red3_.p + 2);
-        launch_reduce_pairs(k5part_.p, k5n(), red3_.p, ctrl_, st_);
-        holdout_finish(k, red3_.p, red3_.p + 2);
-    } else {
-        double* parts = red1_.p + red1_count();
-        const size_t cnt = 2 * (size_t)k5tail_ + 2;
-        holdout_score(parts + 2 * (size_t)k5tail_);
-        allreduce(parts, (int64_t)cnt);
-        launch_reduce_pairs(parts, k5tail_, red3_.p, ctrl_, st_);
-        holdout_finish(k, red3_.p, parts + 2 * (size_t)k5tail_);
-        // (the pairs past this rank's own K5 grid must read zero next time)
-        TRITD_HIP(hipMemsetAsync(parts, 0, cnt * sizeof(double), st_));
-    }
+    const bool sh = sharded();
+    double* parts = norm_parts();
+    const size_t cnt = 2 * (size_t)norm_pairs() + 2;
+    double* score = sh ? parts + cnt - 2 : red3_.p + 2;
+    holdout_score(score);
+    if (sh) allreduce(parts, (int64_t)cnt);
+    launch_reduce_pairs(parts, norm_pairs(), red3_.p, ctrl_, st_);
+    holdout_finish(k, red3_.p, score);
+    // (the pairs past this rank's own K5 grid must read zero next time)
+    if (sh) TRITD_HIP(hipMemsetAsync(parts, 0, cnt * sizeof(double), st_));
     norms_pending_ = false;
 }
 
@@ -1295,7 +1212,7 @@ void Session::run(int iters) {
             // slots: 0 iteration start, 1/2 K2, 3/4 K5, 5 iteration end; at
             // TRITD_TIMING_K5 only 3/4 exist (each record is a stream marker
             // that widens the gap to the next kernel by several us)
-            const bool ar = comm_ && comm_->active();
+            const bool ar = sharded();
             for (int e = 0; e < EV_SLOTS; ++e) {
                 hipEvent_t ev = nullptr;
                 const bool ho = e >= EV_HO;  // the score kernel's pair (holdout sessions)
@@ -1311,10 +1228,8 @@ void Session::run(int iters) {
         Range it_range("tritd:iteration");
         if (fused_) {
             iterate_fused(k);
-        } else if (overlap_) {
-            iterate_overlapped(k);
-        } else if (shov_) {
-            iterate_sharded(k);
+        } else if (overlap_ || shov_) {
+            iterate_side(k);
         } else {
             phaseA(k);
             allreduce(red1_.p, red1_count());

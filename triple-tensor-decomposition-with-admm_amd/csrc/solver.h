@@ -66,6 +66,27 @@ void unpack_C(const Geom& g, const std::vector<double>& Ch, double* C);
 // the n doubles of a device factor through unpack_A/B/C into out (null: nothing)
 void download_factor(const Geom& g, const double* dev, size_t n,
                      void (*unpack)(const Geom&, const std::vector<double>&, double*), double* out);
+// the initial factors through pack_A/B/C into a session's device factors
+// (ChF: C^ in single as well, the fp32 path; null: none)
+void upload_factors(const Geom& g, const double* A0, const double* B0, const double* C0, double* Ah,
+                    double* AhT, double* Bh, double* Ch, double* ChT, float* ChF = nullptr);
+
+// One factor update (update_A/B/C, :77-81,86-88,93-95): Y = M * Ginv and its
+// Gram.  Session::upd(mode) fills it for A, B, C (modes 0, 1, 2).
+struct Update {
+    const double* M = nullptr;  // the right-hand side in double (M2, M3; M1 of the fp64 path)
+    const float* Mf = nullptr;  // or in single (M1 of the fp32 path)
+    int64_t rows = 0;
+    double* Ginv = nullptr;  // the Ginv slot of its solve
+    double* Y = nullptr;     // the factor
+    double* YT = nullptr;    // its transposed copy, leading dimension ldT (null: none)
+    int64_t ldT = 0;
+    float* YF = nullptr;  // its copy in single (C^ of the fp32 path)
+    double* G = nullptr;  // where Y^T Y goes (A^TA behind M2 in red1_, BtB_, CtC_)
+    // the generic apply runs the pinv fallback itself (A only: Session::solve
+    // says why; B and C get it behind the solve, on the solve's stream)
+    bool fix = false;
+};
 
 // What a session is made from: the data of a whole tensor (i0 = 0, i1 = n1) or
 // of one mode-1 shard [i0, i1), the initial factors, the masks and the
@@ -175,13 +196,14 @@ class Session {
     int device() const { return device_; }
 
    private:
+    // a communicator whose all-reduces run (one process per GPU, a host
+    // transport, or a shard of a device group)
+    bool sharded() const { return comm_ && comm_->active(); }
     void allreduce(double* buf, int64_t count);
-    // single-GPU schedule: the three R x R solves run on a side stream, each
-    // overlapped with the big kernel that precedes its consumer
-    void iterate_overlapped(int k);
-    // one process per GPU with RCCL: the phase order with the Grams of B, C
-    // and the solves of C, A(k+1) on the side stream
-    void iterate_sharded(int k);
+    // side-stream schedule: the Grams of B, C and the R x R solves run on a
+    // side stream, each overlapped with the big kernel that precedes its
+    // consumer; with a communicator the same order with its all-reduces
+    void iterate_side(int k);
     // single stream, no events (default for the fp64 CP model at RP <= 64):
     // the solves of update_C and of the next update_A run in an extra
     // workgroup of K2 / K5 (sweep.h), solve B on the main stream; with a
@@ -195,27 +217,33 @@ class Session {
     // must all-reduce the same count); set by agree_counts()
     int k5tail_ = 0;
     void agree_counts();
-    SideSolve k5side_;  // the side solve of the next K5 launch
-    // communicator: K5's norm partials of iteration pend_k_ wait in red1_'s
-    // tail for the next iteration's first all-reduce (one all-reduce fewer
-    // per iteration); flush_norms() all-reduces and finishes them alone
+    // K5's norm partials of iteration pend_k_ wait for the next iteration:
+    // on one GPU in k5part_ for the extra workgroup of its M1 / M2; with a
+    // communicator in red1_'s tail for its first all-reduce (one all-reduce
+    // fewer per iteration); flush_norms() (all-reduces and) finishes them alone
     bool norms_pending_ = false;
     int pend_k_ = 0;
-    double* k5part_to_ = nullptr;  // where the next K5 writes its partials (null: k5part_)
+    double* norm_parts() const { return sharded() ? red1_.p + red1_count() : k5part_.p; }
+    int norm_pairs() const { return sharded() ? k5tail_ : k5n(); }
     void flush_norms();
     bool shov_ = false;
     void create_streams(hipStream_t shared_stream);
+    void side_after_main(hipEvent_t e);
     void launch_k5_full(int k, bool fused_finish);
+    void launch_k5_pending(int k, const SideSolve& side = SideSolve{});
+    // [M2 | A^TA] of this shard: red1_, all-reduced between update_A and update_B
+    double* m2() const { return red1_.p; }
+    double* ata() const { return red1_.p + g_.n2 * g_.RP; }
+    Update upd(int mode) const;
+    void apply(const Update& u);
     bool small_ag(int64_t rows) const;
-    bool apply_gram_A(double* AtA, bool defer = false);
-    bool apply_gram_B(const double* M2, bool defer = false);
-    bool apply_gram_C(bool defer = false);
+    bool apply_gram(const Update& u, bool defer = false);
     bool side_gram_ok() const;
     bool side_gram_bc_ok() const;
     bool gram_a_in_m2() const;
     // the applies take the generic kernel (launch_apply_gen): fp32, or RP > 64
     bool gen_apply() const { return f32_ || g_.RP > 64; }
-    FinishArgs take_finish();
+    FinishArgs take_finish(bool after_allreduce);
     bool overlap_ = false;
     hipStream_t side_ = nullptr;
     hipEvent_t evAtA_ = nullptr, evBtB_ = nullptr, evCtC_ = nullptr;
@@ -228,18 +256,17 @@ class Session {
     DBuf dstage_;  // column-major staging of a host D (creation only)
     std::vector<double> probe_ms_;  // probe time of each candidate pool (ms)
     int probe_pick_ = 0;
-    void upload_factors(const double* A0, const double* B0, const double* C0);
     IterScalars scalars(int k) const;
     IterScalars32 scalars32(int k) const;
     // data-type dispatch of the per-iteration kernels
     void do_m1();
-    void do_m2(double* M2);
+    void do_m2();
     void do_m3();
     void do_m3_qi();
-    void do_apply_A(double* Ginv);
-    void do_apply_B(const double* M2, double* Ginv);
-    void do_apply_C(double* Ginv);
-    void launch_k5_any(int k, bool prologue);
+    // partial: where the fp64 K5 writes its norm partials (null: k5part_);
+    // side: the solve that rides in its extra workgroup
+    void launch_k5_any(int k, bool prologue, double* partial = nullptr,
+                       const SideSolve& side = SideSolve{});
     bool f32_ = false;
     size_t es_ = sizeof(double);  // bytes per element of D, O, E, Y_L, Y_O, T, W, M1
     DBuf ChF_;                    // C^ in single (fp32 path)
@@ -276,7 +303,7 @@ class Session {
     HoldoutSet hset_;
     BestIterate val_;
     // the end of a holdout iteration: score, norm reduction, finish, snapshot
-    // (holdout_tail: the fused and overlapped schedules; the phase schedules
+    // (holdout_tail: the fused and side-stream schedules; the phase schedules
     // call holdout_score after K5 and holdout_finish as their phase D)
     void holdout_tail(int k);
     void holdout_score(double* sums);
@@ -316,9 +343,11 @@ class Session {
     // and the design Grams of the three solves
     bool qi_ = false;
     DBuf H_, ones_, GqA_, GqB_, GqC_;
-    // inv(design Gram + alpha I) of update_A (mode 0), _B (1), _C (2)
-    void solve(int mode, const double* P, const double* Q, double alpha, double* out,
-               hipStream_t s, const FinishArgs* fin = nullptr);
+    // inv(design Gram + alpha I) of update_A (mode 0), _B (1), _C (2): its
+    // operands as the side job of M2 / K2 / K5 carries them (gram: the update
+    // whose Gram that side job forms first), and the solve as a launch on s
+    SideSolve side_solve(int mode, const Update* gram = nullptr) const;
+    void solve(int mode, hipStream_t s, const FinishArgs* fin = nullptr);
     DBuf red1_, red2_, red3_;
     DBuf k5part_, m3part_, sqpart_;
     DBuf errHist_, errL_, errO_;
