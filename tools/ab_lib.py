@@ -1,5 +1,10 @@
 """Dev helper: interleaved in-process A/B of two (or more) builds of libtritd.so.
-usage: python tools/ab_lib.py lib1.so,lib2.so reps [iters]"""
+usage: python tools/ab_lib.py lib1.so,lib2.so reps [iters]
+Per library the medians, and against the first one pair by pair (the sessions
+of one repetition run back to back): the median gain and how many pairs were
+slower.  AB_PROBE=0: no placement probe (every session then takes the first
+pool, which the allocator hands back at the same place from one session to the
+next: less placement noise between the two sides of a pair)."""
 import ctypes as C
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,7 +43,8 @@ res = {p: [] for p in paths}
 for rep in range(reps):
     for p in paths:
         api.lib = _lib.lib = libs[p]
-        s = tritd.Session(r, opts, A0, B0, C0, n1=n1, n2=n2, n3=n3, D=D, device=0)
+        s = tritd.Session(r, opts, A0, B0, C0, n1=n1, n2=n2, n3=n3, D=D, device=0,
+                          probe=os.environ.get("AB_PROBE", "1") != "0")
         s.run(warm); s.sync(); s.set_timing(True); s.run(iters); s.sync()
         km = s.kernel_ms()
         pr = s.probe() if hasattr(libs[p], "tritd_session_probe") else None
@@ -48,3 +54,9 @@ for rep in range(reps):
 for p in paths:
     a = np.array(res[p])
     print("%s median it %.3f k5 %.3f m3 %.3f | min it %.3f" % (p, *np.median(a, 0), a[:, 0].min()))
+base = np.array(res[paths[0]])
+for p in paths[1:]:
+    g = (base - np.array(res[p])) * 1e3  # us gained over the first library, per pair
+    print("%s vs %s: median gain it %+.1f us k5 %+.1f us | pairs slower it %d k5 %d of %d | it gains %s"
+          % (p, paths[0], np.median(g[:, 0]), np.median(g[:, 1]), int((g[:, 0] < 0).sum()),
+             int((g[:, 1] < 0).sum()), len(g), " ".join("%+.0f" % x for x in g[:, 0])))

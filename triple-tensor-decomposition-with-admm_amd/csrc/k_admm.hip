@@ -82,6 +82,14 @@ static constexpr int K5_NT_AUX = 2;
 #define TRITD_STORE_KEEP 1
 #endif
 
+// The same hint on the loads of the compact-E slots (and of an overflowed
+// tile's values): 0.27 GB per launch that would otherwise pass through the
+// Infinity Cache, in which the 134 MB of W have to survive until M1 and M2
+// (profiles/k5_step_regions/: iteration -16 us against the plain loads).  The
+// slot store stays plain: with the hint K5 took ~10 us longer and the
+// iteration gained nothing.
+static constexpr int K5_SLOT_LD_AUX = K5_NT_AUX;
+
 #if TRITD_WTRACE
 WT_DECL(g_wt_k5)
 #endif
@@ -137,8 +145,12 @@ __device__ __forceinline__ bool ce_decode(double sv, int lane, double* img, doub
 // Store this lane's 4 elements of E (register order) as the tile's slot
 // (buffer rs at scalar offset soff), or densely into E2 at d2v offset o when
 // they do not fit.  cs: the wave's 96-double LDS scratch (slot image + a junk
-// area for the zeros).  Branch-free: a branch here makes the compiler's
-// vmcnt waits drain the prefetch.
+// area for the zeros).  One basic block up to the rare dense store: every
+// lane condition is a select on a wave-uniform mask (`!dense && bit`
+// compiled to a scalar branch per mask word, and `if (lane == 0)` to a
+// lane-masked stretch: seven blocks, none of which the scheduler could fill;
+// DESIGN.md §4.2), and a branch with anything but stores in it makes the
+// compiler's vmcnt waits drain the prefetch.
 __device__ __forceinline__ void ce_encode(const double (&En)[4], int lane, double* cs,
                                           __amdgpu_buffer_rsrc_t rs, int soff, d2v* E2, int64_t o,
                                           unsigned& ndense) {
@@ -157,13 +169,14 @@ __device__ __forceinline__ void ce_encode(const double (&En)[4], int lane, doubl
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     unsigned char* cb = reinterpret_cast<unsigned char*>(cs);
+    const uint64_t keepmask = dense ? 0ull : ~0ull;
     int pre = 0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
         // (a dense tile's image is not used: its values and bytes go to the
         // junk area).  The wave-uniform mask itself is the lane condition
         // (inverse ballot: one select, no shift/and/compare).
-        const bool bit = !dense && __builtin_amdgcn_inverse_ballot_w64(nz[w]);
+        const bool bit = __builtin_amdgcn_inverse_ballot_w64(nz[w] & keepmask);
         // One select for both writes: a lane with no value writes word 32 +
         // lane and byte CE_IDX_BYTE + 32 + lane (word 31 and up: the count
         // word, written after this loop in the same wave's LDS order, and the
@@ -176,7 +189,8 @@ __device__ __forceinline__ void ce_encode(const double (&En)[4], int lane, doubl
         cb[CE_IDX_BYTE + sel] = (unsigned char)(64 * w + lane);
         pre += __builtin_popcountll(nz[w]);
     }
-    if (lane == 0) cs[CE_CNT_WORD] = __longlong_as_double(dense ? 0xFFFFFFFFll : (long long)cnt);
+    // the count, by the same select: every lane but lane 0 writes its junk word
+    cs[lane == 0 ? CE_CNT_WORD : 32 + lane] = __longlong_as_double(dense ? 0xFFFFFFFFll : (long long)cnt);
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     const double v = cs[l];
@@ -186,9 +200,10 @@ __device__ __forceinline__ void ce_encode(const double (&En)[4], int lane, doubl
     if (dense) {
         E2[o] = d2v{En[0], En[1]};
         E2[o + 64] = d2v{En[2], En[3]};
-        ++ndense;  // wave-uniform; one atomic per wave at the end (a per-tile
-                   // atomic on one counter serialised: 17 -> 53 ms once E turned dense)
     }
+    // wave-uniform; one atomic per wave at the end (a per-tile atomic on one
+    // counter serialised: 17 -> 53 ms once E turned dense)
+    ndense += dense ? 1u : 0u;
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), rs, lane < 32 ? l * 8 : OOB,
                                           soff, 0);
 }
@@ -428,8 +443,10 @@ void k5_fused(K5Args a) {
     auto load_slot = [&](int64_t tt, Regs& rx) {
         if constexpr (DE || PRO) return;
         const int so = (int)((tt < ntt ? tt : ntt - 1) * 1024);  // clamped: no branch
-        rx.ce = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rCE, vslot, so, 0));
-        rx.cep = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rCEp, vslot, so, 0));
+        rx.ce = __builtin_bit_cast(
+            double, __builtin_amdgcn_raw_buffer_load_b64(rCE, vslot, so, K5_SLOT_LD_AUX));
+        rx.cep = __builtin_bit_cast(
+            double, __builtin_amdgcn_raw_buffer_load_b64(rCEp, vslot, so, K5_SLOT_LD_AUX));
     };
 
     // one t-tile: cx holds its data, `buf` its C^ slice; if `pf`, tile tt+1 is
@@ -442,7 +459,10 @@ void k5_fused(K5Args a) {
     auto dense_fix = [&](int64_t tt, bool dn, bool dp, double (&ev)[4], double (&evp)[4]) {
         if (dn || dp) {
             const int64_t od = (tm_tile_base(tile, tt, ntt) >> 1) + lane;
-            const d2v a0 = E2[od], a1 = E2[od + 64], b0 = Ep2[od], b1 = Ep2[od + 64];
+            const d2v a0 = __builtin_nontemporal_load(E2 + od);
+            const d2v a1 = __builtin_nontemporal_load(E2 + od + 64);
+            const d2v b0 = __builtin_nontemporal_load(Ep2 + od);
+            const d2v b1 = __builtin_nontemporal_load(Ep2 + od + 64);
             ev[0] = dn ? a0[0] : ev[0];
             ev[1] = dn ? a0[1] : ev[1];
             ev[2] = dn ? a1[0] : ev[2];
@@ -477,6 +497,20 @@ void k5_fused(K5Args a) {
         // sinks it next to the stores (less register pressure, no latency
         // hiding)
         __builtin_amdgcn_sched_barrier(0);
+        // L^T(t, ij) of this t-tile: KS dependent MFMAs.  In the compact-E
+        // form they come first in source order: they need nothing from E, and
+        // the compiler then issues the two decodes' LDS round trips between
+        // them instead of ahead of the chain (tools/k5_regions.py; with the
+        // encode as one block K5 -15 us, profiles/k5_step_regions/).  RP <=
+        // 64 only: at RP = 256 the masked form has no register left for the
+        // longer life of lacc (256 VGPRs + 256 AGPRs: it spilled one).
+        constexpr bool LFIRST = !DE && !PRO && RP <= 64;
+        d4 lacc = {0.0, 0.0, 0.0, 0.0};
+        auto lchain = [&]() {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) lacc = mfma4(opL(buf, s), kr[s], lacc);
+        };
+        if constexpr (LFIRST) lchain();
         double ev[4], evp[4];
         bool dn = false, dp = false;
         if constexpr (DE) {
@@ -520,10 +554,7 @@ void k5_fused(K5Args a) {
                     tr[2 * p + q] = (d - ov) + sc.invL * yl;  // :33
                 }
         } else {
-            // L^T(t, ij) of this t-tile: KS dependent MFMAs
-            d4 lacc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) lacc = mfma4(opL(buf, s), kr[s], lacc);
+            if constexpr (!LFIRST) lchain();
             // MK: the tile's mask words, wave-uniform (the lane condition below
             // is their inverse ballot, as in ce_encode)
             uint64_t ob[4] = {0, 0, 0, 0};
