@@ -707,6 +707,68 @@ tritd_status tritd_dev_quality_f64(const double* X1, const double* X2, int64_t n
                                    int64_t nf, double* psnr, double* ssim, double* psnr_frames,
                                    double* ssim_frames, void* stream);
 
+/* Foreground detection: eval(origin, groundtruth, background, foreground) of
+ * video_triple_comparison.m:316-371.  With F the foreground,
+ * G the CDnet labels (uint8: 255 = motion, 170 = unknown) and thr the
+ * threshold (the reference's is 50, :339):
+ *   p = abs(F) > thr (strict; NaN false, +-Inf true; a single F is widened),
+ *   g = (G == 255), m = (G == 170), and per frame t (:347-360)
+ *   TP = #(p & (g|m)), FP = #(p & ~g), FN = #(~p & g), TN = #(~p & (~g|m)).
+ * pred receives p as bytes 0/1; counts is int64[nf][4] in the order TP, FP,
+ * FN, TN, exact.  gt NULL: no counts (counts is not touched); pred NULL: no
+ * mask; both NULL is TRITD_ERR_ARG, and so is thr < 0 or NaN.  The graythresh
+ * level of :335-336 is computed and never used by the reference; it is not
+ * restated.
+ *
+ * Session forms (video_triple_comparison.m:316-371 on the session's own O):
+ * F is the O that tritd_session_get / tritd_als_session_get_O would return at
+ * that moment (0 before the first ADMM iteration), thresholded where the
+ * session keeps it: an ADMM session forms each element from its resident D,
+ * Y_L and T and never materialises, converts or downloads O.  gt and pred
+ * point at the byte of element (i0, 0, 0) of column-major arrays whose fibres
+ * are ldG / ldP bytes apart (both >= i1 - i0); bytes of pred outside the
+ * shard's rows are not written.  counts (host memory, n3 x 4) holds the
+ * shard's rows only: a caller with several shards adds them, as it does the
+ * parts of tritd_session_rre_parts; nothing is reduced across ranks.  With
+ * TRITD_FG_DEVICE in flags gt and pred are device pointers on the session's
+ * device, else host pointers staged through device buffers.  The call waits
+ * for the session stream and leaves the session's state untouched.  The ALS
+ * form is TRITD_ERR_STATE on a session that is not nonconvex. */
+enum { TRITD_FG_DEVICE = 1u }; /* gt and pred are device pointers on the session's device */
+tritd_status tritd_session_foreground(tritd_session* s, double thr, const uint8_t* gt, int64_t ldG,
+                                      uint8_t* pred, int64_t ldP, int64_t* counts, uint32_t flags);
+tritd_status tritd_als_session_foreground(tritd_als_session* s, double thr, const uint8_t* gt,
+                                          int64_t ldG, uint8_t* pred, int64_t ldP, int64_t* counts,
+                                          uint32_t flags);
+/* ms of the kernel of the last tritd_session_foreground (eval of
+ * video_triple_comparison.m:316-371) made while tritd_session_set_timing was
+ * on, from HIP events around its launch: the staging copies and the wait are
+ * not in it.  0 before the first such call. */
+tritd_status tritd_session_foreground_ms(tritd_session* s, double* kernel_ms);
+/* eval of video_triple_comparison.m:316-371 on a column-major n1 x n2 x nf
+ * tensor F (double or single) in host memory; gt and pred are n1*n2*nf bytes. */
+tritd_status tritd_foreground_f64(const double* F, const uint8_t* gt, int64_t n1, int64_t n2,
+                                  int64_t nf, double thr, uint8_t* pred, int64_t* counts);
+tritd_status tritd_foreground_f32(const float* F, const uint8_t* gt, int64_t n1, int64_t n2,
+                                  int64_t nf, double thr, uint8_t* pred, int64_t* counts);
+/* The same (video_triple_comparison.m:316-371) on device pointers F, gt and
+ * pred with leading dimensions (element (i,j,t) at i + ld*(j + n2*t), each ld
+ * >= n1); counts is host memory and the call waits for the stream. */
+tritd_status tritd_dev_foreground_f64(const double* F, int64_t ldF, const uint8_t* gt, int64_t ldG,
+                                      int64_t n1, int64_t n2, int64_t nf, double thr, uint8_t* pred,
+                                      int64_t ldP, int64_t* counts, void* stream);
+tritd_status tritd_dev_foreground_f32(const float* F, int64_t ldF, const uint8_t* gt, int64_t ldG,
+                                      int64_t n1, int64_t n2, int64_t nf, double thr, uint8_t* pred,
+                                      int64_t ldP, int64_t* counts, void* stream);
+/* The scores of video_triple_comparison.m:316-371 (:356-365) from per-frame
+ * counts[nf][4]: total = the sums over frames (TP, FP, FN, TN), precision =
+ * TP/(TP+FP), recall = TP/(TP+FN), f1 = 2PR/(P+R), pwc = 100 (FP+FN)/numel,
+ * in double; 0/0 is NaN as in MATLAB.  Host arithmetic only (no device is
+ * needed); total and each score pointer may be NULL. */
+tritd_status tritd_foreground_scores(const int64_t* counts, int64_t nf, int64_t numel,
+                                     int64_t total[4], double* precision, double* recall,
+                                     double* f1, double* pwc);
+
 /* Device-pointer variants (for device-resident callers and the bench). */
 tritd_status tritd_dev_unfold_f64(const double* X, int64_t n1, int64_t n2, int64_t n3, int32_t mode,
                                   double* Xn, void* stream);

@@ -498,4 +498,21 @@ void AlsSession::get_O(double* O, int64_t ldO) {
     }
 }
 
+void AlsSession::foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t* pred, int64_t ldP,
+                            int64_t* counts, bool on_device) {
+    int done = 0, stopped = 0;
+    sync(&done, &stopped);
+    if (!ncvx_) throw Error(TRITD_ERR_STATE, "foreground: not a nonconvex (test.m) session");
+    const int kk = stopped ? done - 1 : done;  // the O of get_O
+    FgArgs a;
+    a.thr = thr;
+    a.D = (kk & 1) ? Ob_.p : Oa_.p;
+    run_foreground(g_.n1l, g_.n2 * g_.n3, g_.n3, gt, ldG, pred, ldP, counts, on_device, st_,
+                   [&](const uint8_t* dg, int64_t ldg, uint8_t* dp, int64_t ldp,
+                       unsigned long long* dc) {
+                       a.gt = dg; a.ldG = ldg; a.pred = dp; a.ldP = ldp; a.counts = dc;
+                       launch_foreground_tm(g_, FG_STORED64, a, st_);
+                   });
+}
+
 }  // namespace tritd

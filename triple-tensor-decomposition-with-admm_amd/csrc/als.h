@@ -99,6 +99,9 @@ class AlsSession {
     // O returned by test.m: that of iteration k-1 when the stop test broke
     // the loop at k (:67 before :71), else the last one; column-major shard
     void get_O(double* O, int64_t ldO);
+    // Session::foreground (solver.h) on the O of get_O, read where it is stored
+    void foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t* pred, int64_t ldP,
+                    int64_t* counts, bool on_device);
 
     // --- phase interface (device groups drive these; see api.cpp) -------
     int next_iter();

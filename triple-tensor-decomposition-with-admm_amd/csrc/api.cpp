@@ -1816,4 +1816,130 @@ tritd_status tritd_quality_f64(const double* X1, const double* X2, int64_t n1, i
     });
 }
 
+// ---------------------------------------------------------------------------
+// foreground detection (video_triple_comparison.m:316-371)
+// ---------------------------------------------------------------------------
+// the rules every form shares, after its own first ones (session / F, dims)
+static void rule_fg_outputs(double thr, const uint8_t* gt, const uint8_t* pred,
+                            const int64_t* counts) {
+    if (!(thr >= 0.0)) throw Error(TRITD_ERR_ARG, "thr must be >= 0 (and not NaN)");
+    if (!gt && !pred) throw Error(TRITD_ERR_ARG, "gt and pred are both NULL: nothing to compute");
+    if (gt) need(counts, "counts");
+}
+static void rule_fg_ld(const void* p, int64_t ld, int64_t rows, const char* name, const char* of) {
+    if (p && ld < rows) throw Error(TRITD_ERR_ARG, std::string(name) + " smaller than " + of);
+}
+
+// thr, outputs and leading dimensions of a session form, then the call itself
+#define TRITD_SESSION_FOREGROUND(sess)                                                  \
+    do {                                                                                \
+        rule_fg_outputs(thr, gt, pred, counts);                                         \
+        rule_fg_ld(gt, ldG, (sess)->geom().n1l, "ldG", "the shard");                    \
+        rule_fg_ld(pred, ldP, (sess)->geom().n1l, "ldP", "the shard");                  \
+        (sess)->foreground(thr, gt, ldG, pred, ldP, counts, (flags & TRITD_FG_DEVICE) != 0); \
+    } while (0)
+
+tritd_status tritd_session_foreground(tritd_session* s, double thr, const uint8_t* gt, int64_t ldG,
+                                      uint8_t* pred, int64_t ldP, int64_t* counts, uint32_t flags) {
+    return guarded([&] {
+        Session* S = admm(s);
+        TRITD_SESSION_FOREGROUND(S);
+    });
+}
+
+tritd_status tritd_als_session_foreground(tritd_als_session* s, double thr, const uint8_t* gt,
+                                          int64_t ldG, uint8_t* pred, int64_t ldP, int64_t* counts,
+                                          uint32_t flags) {
+    return guarded([&] {
+        AlsSession* as = als(s);
+        if (!as->ncvx()) throw Error(TRITD_ERR_STATE, "foreground: not a nonconvex (test.m) session");
+        TRITD_SESSION_FOREGROUND(as);
+    });
+}
+#undef TRITD_SESSION_FOREGROUND
+
+tritd_status tritd_session_foreground_ms(tritd_session* s, double* kernel_ms) {
+    return guarded([&] {
+        Session* S = admm(s);
+        need(kernel_ms, "kernel_ms");
+        *kernel_ms = S->foreground_ms();
+    });
+}
+
+static void dev_foreground(const void* F, bool f32, int64_t ldF, const uint8_t* gt, int64_t ldG,
+                           int64_t n1, int64_t n2, int64_t nf, double thr, uint8_t* pred,
+                           int64_t ldP, int64_t* counts, void* stream, bool on_device) {
+    need(F, "F");
+    if (n1 <= 0 || n2 <= 0 || nf <= 0) throw Error(TRITD_ERR_ARG, "sizes must be positive");
+    rule_fg_outputs(thr, gt, pred, counts);
+    rule_fg_ld(F, ldF, n1, "ldF", "n1");
+    rule_fg_ld(gt, ldG, n1, "ldG", "n1");
+    rule_fg_ld(pred, ldP, n1, "ldP", "n1");
+    DBuf dF;
+    hipStream_t st = as_stream(stream);
+    if (on_device) {
+        hip_entry();  // device pointers from the caller: HIP is in use
+    } else {
+        pick_device(-1);
+        const size_t nb = (size_t)(n1 * n2 * nf) * (f32 ? sizeof(float) : sizeof(double));
+        dF.alloc_bytes(nb);
+        TRITD_HIP(hipMemcpyAsync(dF.p, F, nb, hipMemcpyHostToDevice, st));
+        F = dF.p;
+    }
+    run_foreground(n1, n2 * nf, nf, gt, ldG, pred, ldP, counts, on_device, st,
+                   [&](const uint8_t* dg, int64_t ldg, uint8_t* dp, int64_t ldp,
+                       unsigned long long* dc) {
+                       launch_foreground_cm(F, f32, ldF, dg, ldg, dp, ldp, dc, n1, n2, nf, thr, st);
+                   });
+}
+
+tritd_status tritd_dev_foreground_f64(const double* F, int64_t ldF, const uint8_t* gt, int64_t ldG,
+                                      int64_t n1, int64_t n2, int64_t nf, double thr, uint8_t* pred,
+                                      int64_t ldP, int64_t* counts, void* stream) {
+    return guarded([&] {
+        dev_foreground(F, false, ldF, gt, ldG, n1, n2, nf, thr, pred, ldP, counts, stream, true);
+    });
+}
+
+tritd_status tritd_dev_foreground_f32(const float* F, int64_t ldF, const uint8_t* gt, int64_t ldG,
+                                      int64_t n1, int64_t n2, int64_t nf, double thr, uint8_t* pred,
+                                      int64_t ldP, int64_t* counts, void* stream) {
+    return guarded([&] {
+        dev_foreground(F, true, ldF, gt, ldG, n1, n2, nf, thr, pred, ldP, counts, stream, true);
+    });
+}
+
+tritd_status tritd_foreground_f64(const double* F, const uint8_t* gt, int64_t n1, int64_t n2,
+                                  int64_t nf, double thr, uint8_t* pred, int64_t* counts) {
+    return guarded([&] {
+        dev_foreground(F, false, n1, gt, n1, n1, n2, nf, thr, pred, n1, counts, nullptr, false);
+    });
+}
+
+tritd_status tritd_foreground_f32(const float* F, const uint8_t* gt, int64_t n1, int64_t n2,
+                                  int64_t nf, double thr, uint8_t* pred, int64_t* counts) {
+    return guarded([&] {
+        dev_foreground(F, true, n1, gt, n1, n1, n2, nf, thr, pred, n1, counts, nullptr, false);
+    });
+}
+
+tritd_status tritd_foreground_scores(const int64_t* counts, int64_t nf, int64_t numel,
+                                     int64_t total[4], double* precision, double* recall,
+                                     double* f1, double* pwc) {
+    return guarded([&] {
+        if (nf < 0 || numel < 0) throw Error(TRITD_ERR_ARG, "sizes must be >= 0");
+        if (nf > 0) need(counts, "counts");
+        int64_t tot[4] = {0, 0, 0, 0};  // :356-359
+        for (int64_t t = 0; t < nf; ++t)
+            for (int q = 0; q < 4; ++q) tot[q] += counts[4 * t + q];
+        const double TP = (double)tot[0], FP = (double)tot[1], FN = (double)tot[2];
+        const double P = TP / (TP + FP);             // :362
+        const double R = TP / (TP + FN);             // :363
+        const double F1 = 2.0 * P * R / (P + R);     // :364
+        const double PWC = 100.0 * (FP + FN) / (double)numel;  // :365
+        if (total) std::copy(tot, tot + 4, total);
+        put(precision, P); put(recall, R); put(f1, F1); put(pwc, PWC);
+    });
+}
+
 }  // extern "C"

@@ -50,6 +50,7 @@
 // fixed-order tree), never MATLAB's.
 #include "finish.h"
 #include "kernels.h"
+#include "o_expr.h"
 #include "sweep.h"
 #include "wtrace.h"
 
@@ -928,7 +929,7 @@ __global__ __launch_bounds__(256) void k_o_fixup(const double* __restrict__ D,
         const int il = l & 15, tl = (l >> 4) + 4 * r;  // element of this TM slot
         const int s = il >> 2, lx = ((il & 3) << 4) | tl;  // its TX slot
         const int64_t tx = (e & ~(int64_t)255) + ((s >> 1) << 7) + (lx << 1) + (s & 1);
-        const double v = (D[e] + invL_next * YL[e]) - T[tx];
+        const double v = o_expr(D[e], YL[e], T[tx], invL_next);
         const bool obs = !M || ((M[((e >> 8) << 2) + r] >> l) & 1ull);
         O[e] = obs ? v : 0.0;
     }

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "o_expr.h"
 
 namespace tritd {
 
@@ -922,8 +923,7 @@ __global__ __launch_bounds__(256) void k_o_fixup32(const float* __restrict__ D,
         const int l = w >> 2, r = w & 3;
         const int t = 4 * (l >> 4) + r, ii = l & 15;
         const int tx = 4 * (((ii & 3) << 4) | t) + (ii >> 2);
-        const double v = ((double)D[e] + (double)invL_next * (double)YL[e]) - (double)T[base + tx];
-        O[e] = (float)v;
+        O[e] = o_value32(D[e], YL[e], T[base + tx], invL_next);
     }
 }
 

@@ -4,6 +4,8 @@
 // become no-ops without a host round trip.
 #pragma once
 
+#include <functional>
+
 #include "common.h"
 
 namespace tritd {
@@ -346,6 +348,52 @@ size_t quality_scratch(int64_t n1, int64_t n2, int64_t nf);
 void launch_quality(const double* X, const double* Y, int64_t n1, int64_t n2, int64_t nf,
                     const double* win, double C1, double C2, double* scratch, double* psnr,
                     double* ssim, hipStream_t st);
+
+// ---- foreground detection (k_foreground.hip) ------------------
+// eval of video_triple_comparison.m:316-371: pred = abs(F) > thr as bytes,
+// counts[t][0..3] += TP, FP, FN, TN of frame t against the labels gt
+// (255 = motion, 170 = unknown).  gt null: no counts; pred null: no mask.
+// Where the tile-major form takes F from:
+enum FgSource {
+    FG_ADMM64 = 0,    // (D + invL_next Y_L) - T of an fp64 ADMM session (o_expr.h), 0 where M says unobserved
+    FG_ADMM32 = 1,    // the same of an fp32 session, rounded to single
+    FG_STORED64 = 2,  // a stored tile-major tensor, passed as D
+    FG_ZERO = 3       // F = 0: nothing is read
+};
+struct FgArgs {
+    const void* D = nullptr;
+    const void* YL = nullptr;
+    const void* T = nullptr;  // TX order
+    double invL_next = 0.0;
+    float invL_next32 = 0.0f;
+    const unsigned long long* M = nullptr;  // mask words (common.h: MK) or null
+    double thr = 0.0;
+    // column-major bytes of the shard: element (i, j, t) at i + ld (j + n2 t)
+    const uint8_t* gt = nullptr;
+    int64_t ldG = 0;
+    uint8_t* pred = nullptr;
+    int64_t ldP = 0;
+    unsigned long long* counts = nullptr;  // [n3][4], zero on entry
+    // filled by the launcher from the geometry
+    int64_t n1l = 0, n1p = 0, n2 = 0, n3 = 0, tiles = 0, ntt = 0;
+    int vec = 0;
+};
+void launch_foreground_tm(const Geom& g, int src, const FgArgs& a, hipStream_t st);
+// plain column-major F (double, or float when f32) of n1 x n2 x nf
+void launch_foreground_cm(const void* F, bool f32, int64_t ldF, const uint8_t* gt, int64_t ldG,
+                          uint8_t* pred, int64_t ldP, unsigned long long* counts, int64_t n1,
+                          int64_t n2, int64_t nf, double thr, hipStream_t st);
+// The host side of one call: a host gt (on_device = false) is staged into a
+// device buffer of rows*cols bytes, the device counts are zeroed, `launch`
+// runs with the device gt / pred / counts and their leading dimensions, then
+// pred (rows bytes of each of the cols fibres) and counts[nf][4] return to the
+// host and the stream is waited for.  kernel_ms (or null) receives the
+// kernel's own time from events recorded around its launch.
+void run_foreground(int64_t rows, int64_t cols, int64_t nf, const uint8_t* gt, int64_t ldG,
+                    uint8_t* pred, int64_t ldP, int64_t* counts, bool on_device, hipStream_t st,
+                    const std::function<void(const uint8_t*, int64_t, uint8_t*, int64_t,
+                                             unsigned long long*)>& launch,
+                    double* kernel_ms = nullptr);
 
 // ---------------------------------------------------------------------------
 // fp32 data path (D of class single): T, O, E, Y_L, Y_O, W and

@@ -1398,6 +1398,29 @@ void Session::get(double* A, double* B, double* C, void* O, void* E, int64_t ldO
     if (iters) *iters = done;
 }
 
+void Session::foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t* pred, int64_t ldP,
+                         int64_t* counts, bool on_device) {
+    int done = 0;
+    sync(&done, nullptr);
+    FgArgs a;
+    a.thr = thr;
+    a.D = D_.p; a.YL = YL_.p; a.T = T_.p;
+    // the scalar and the mask words of get()'s fix-up; nothing of the session is written
+    if (done > 0) {
+        a.invL_next = 1.0 / mu_[(size_t)done];
+        a.invL_next32 = (float)a.invL_next;
+    }
+    a.M = f32_ ? nullptr : mask_words();
+    const int src = done == 0 ? FG_ZERO : (f32_ ? FG_ADMM32 : FG_ADMM64);
+    run_foreground(g_.n1l, g_.n2 * g_.n3, g_.n3, gt, ldG, pred, ldP, counts, on_device, st_,
+                   [&](const uint8_t* dg, int64_t ldg, uint8_t* dp, int64_t ldp,
+                       unsigned long long* dc) {
+                       a.gt = dg; a.ldG = ldg; a.pred = dp; a.ldP = ldp; a.counts = dc;
+                       launch_foreground_tm(g_, src, a, st_);
+                   },
+                   timing_ ? &fg_ms_ : nullptr);
+}
+
 void Session::get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason) {
     int done = 0;
     sync(&done, nullptr);

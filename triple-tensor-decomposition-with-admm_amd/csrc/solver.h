@@ -162,6 +162,17 @@ class Session {
     // ms per timed iteration (TRITD_TIMING_ALL) in the score kernel, and from
     // the end of K5 to the end of the iteration (score, reductions, finish, snapshot)
     void holdout_ms(double* score, double* tail) const { val_.holdout_ms(acc_n_, score, tail); }
+    // eval of video_triple_comparison.m:316-371 on the O that get() would
+    // return now: pred = abs(O) > thr as column-major bytes of
+    // the shard (fibres ldP apart; null: none), counts[n3][4] = TP, FP, FN, TN
+    // per frame against the labels gt (fibres ldG apart; null: none).
+    // on_device: gt and pred are device pointers.  O is not materialised and
+    // nothing of the session is written; waits for the stream.
+    void foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t* pred, int64_t ldP,
+                    int64_t* counts, bool on_device);
+    // ms of the kernel of the last foreground() made with timing on (events
+    // around its launch; 0 before the first)
+    double foreground_ms() const { return fg_ms_; }
     // doubles of red3 reduced over the shards at creation (normD^2, the fit
     // count; holdout: + ||H o Omega o D||^2, the held-out count, sum |.|) and in
     // every iteration of the phase schedules (holdout: + the two score sums)
@@ -359,6 +370,7 @@ class Session {
     }
 
     int timing_ = 0;
+    double fg_ms_ = 0.0;
     // timing event `slot` of this iteration (null: not timed), and its record
     hipEvent_t ev_slot(int slot) const {
         return timing_ ? ev_[ev_.size() - EV_SLOTS + slot] : nullptr;

@@ -16,6 +16,8 @@ from .api import (  # noqa: F401
     buildG,
     buildH,
     evaluate,
+    foreground_eval,
+    foreground_scores,
     initial_factors,
     make_opts,
     quality_ybz,

@@ -33,6 +33,7 @@ SESSION_D_ON_DEVICE = 1
 SESSION_F32 = 2
 SESSION_PROBE = 4
 FLAG_PINV_TOL = 1  # TRITD_FLAG_PINV_TOL (include/tritd.h)
+FG_DEVICE = 1  # TRITD_FG_DEVICE (include/tritd.h)
 
 
 class TritdError(RuntimeError):
@@ -173,6 +174,17 @@ SIGNATURES = {
     "tritd_als_session_get_val2": (C.c_int, [vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
     "tritd_als_session_holdout_ms": (C.c_int, [vp, dp, dp]),
     "tritd_dev_triple_product_qi_f64": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, vp, vp]),
+    # foreground detection (video_triple_comparison.m:316-371)
+    "tritd_session_foreground": (C.c_int, [vp, C.c_double, vp, i64, vp, i64, vp, C.c_uint32]),
+    "tritd_als_session_foreground": (C.c_int, [vp, C.c_double, vp, i64, vp, i64, vp, C.c_uint32]),
+    "tritd_session_foreground_ms": (C.c_int, [vp, dp]),
+    "tritd_foreground_f64": (C.c_int, [vp, vp, i64, i64, i64, C.c_double, vp, vp]),
+    "tritd_foreground_f32": (C.c_int, [vp, vp, i64, i64, i64, C.c_double, vp, vp]),
+    "tritd_dev_foreground_f64": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_double, vp, i64, vp,
+                                           vp]),
+    "tritd_dev_foreground_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_double, vp, i64, vp,
+                                           vp]),
+    "tritd_foreground_scores": (C.c_int, [vp, i64, i64, vp, dp, dp, dp, dp]),
 }
 
 # Entry points whose name carries a MATLAB variable's capital letter.  Bound

@@ -13,6 +13,7 @@ the MATLAB file it replaces and runs on the GPU through libtritd.so:
     soft_threshold(X, lam)                  soft_threshold.m:1
     buildF(B, C) / buildG(A, C) / buildH(A, B)   buildF.m:1 / buildG.m:1 / buildH.m:1
     evaluate(X, gt, mask)                   traffic_triple_comparison.m:194-202
+    foreground_eval(F, groundtruth, thr)    video_triple_comparison.m:316-371 (eval)
     quality_ybz(X1, X2)                     other_methods/Low-rank-.../quality_ybz.m:1
 
 Arrays are numpy, MATLAB (column-major) semantics.  `opts` is a dict (or any
@@ -487,6 +488,70 @@ def quality_ybz(imagery1, imagery2, per_frame=False):
     return p.value, s.value
 
 
+def _label_bytes(groundtruth, shape, what="groundtruth"):
+    """CDnet labels as bytes.  Only 255 (motion) and 170 (unknown) are ever
+    compared (video_triple_comparison.m:342-343), so an array of another type
+    keeps exactly those two values and becomes 0 elsewhere.  A uint8 array
+    whose strides are those of a column-major array with a larger leading
+    dimension (rows i0:i1 of the whole ground truth) is used where it lies.
+    -> (array to keep alive, leading dimension)"""
+    G = np.asarray(groundtruth)
+    if tuple(G.shape) != tuple(shape):
+        raise ValueError(f"{what} must have the shape {tuple(shape)}, got {tuple(G.shape)}")
+    if G.dtype != np.uint8:
+        G = np.where(G == 255, 255, np.where(G == 170, 170, 0)).astype(np.uint8)
+    if G.ndim == 3 and G.size and G.strides[0] == 1:
+        ld = G.strides[1]
+        if ld >= G.shape[0] and G.strides == (1, ld, ld * G.shape[1]):
+            return G, int(ld)
+    G = np.asfortranarray(G)
+    return G, int(G.shape[0]) if G.ndim else 1
+
+
+def foreground_scores(counts, numel):
+    """The scores of eval (video_triple_comparison.m:356-365) from per-frame
+    counts (nf, 4) in the order TP, FP, FN, TN: dict(total=int64[4], precision,
+    recall, f1, pwc), in double; 0/0 is NaN as in MATLAB.  Host arithmetic in
+    the library (tritd_foreground_scores): no device is needed."""
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.int64).reshape(-1, 4))
+    total = np.zeros(4, dtype=np.int64)
+    v = [C.c_double(0) for _ in range(4)]
+    check(lib.tritd_foreground_scores(_ptr(c), c.shape[0], int(numel), _ptr(total),
+                                      *(C.byref(x) for x in v)))
+    return dict(total=total, precision=v[0].value, recall=v[1].value, f1=v[2].value,
+                pwc=v[3].value)
+
+
+def foreground_eval(F, groundtruth=None, thr=50.0):
+    """eval(origin, groundtruth, background, foreground) of
+    video_triple_comparison.m:316-371 on the GPU: ``mask = abs(F) > thr``
+    (strict; NaN False) and, with a ground truth of CDnet labels (255 = motion,
+    170 = unknown), the per-frame ``counts`` (nf, 4) = TP, FP, FN, TN with
+    their ``total`` and ``precision``, ``recall``, ``f1``, ``pwc``.  F is
+    float64 or float32 (anything else is taken as float64); dimensions past
+    the second are folded into frames, as ``quality_ybz`` does.  Without a
+    ground truth only ``mask`` is returned."""
+    F = np.asarray(F)
+    f32 = F.dtype == np.float32
+    F = np.asfortranarray(F, dtype=np.float32 if f32 else np.float64)
+    if F.ndim == 0:
+        F = F.reshape(1)
+    n1 = F.shape[0]
+    n2 = F.shape[1] if F.ndim > 1 else 1
+    nf = max(F.size // max(n1 * n2, 1), 1)
+    G = None
+    if groundtruth is not None:
+        G = np.asfortranarray(_label_bytes(groundtruth, F.shape)[0])
+    mask = np.zeros(F.shape, dtype=np.uint8, order="F")
+    counts = np.zeros((nf, 4), dtype=np.int64)
+    fn = lib.tritd_foreground_f32 if f32 else lib.tritd_foreground_f64
+    check(fn(_ptr(F), _ptr(G), n1, n2, nf, float(thr), _ptr(mask), _ptr(counts)))
+    out = dict(mask=mask.view(np.bool_))
+    if G is not None:
+        out.update(counts=counts, **foreground_scores(counts, F.size))
+    return out
+
+
 def _design(which, P, Q, nP, nQ, r):
     out = np.zeros((r * r, nP * nQ), order="F")
     check(lib.tritd_build_design_f64(which.encode(), _ptr(P), _ptr(Q), nP, nQ, r, _ptr(out)))
@@ -594,6 +659,49 @@ class _SessionBase:
         A, B, Cf = self._factors()
         check(self._fn("get_best")(self._s, _ptr(A), _ptr(B), _ptr(Cf)))
         return dict(A=A, B=B, C=Cf)
+
+    def foreground(self, thr=50.0, groundtruth=None, *, return_mask=True, gt_device_ptr=None,
+                   mask_device_ptr=None, ldG=None, ldP=None):
+        """eval of video_triple_comparison.m:316-371 on the session's own O
+        (tritd_session_foreground / tritd_als_session_foreground): the O that
+        ``get()`` / ``get_O()`` would return now, thresholded on the device
+        where the session keeps it, so O is never rebuilt, converted or
+        downloaded.  -> dict(mask=bool (nl, n2, n3) column-major, counts=int64
+        (n3, 4) as TP, FP, FN, TN of the shard's rows, total, precision, recall,
+        f1, pwc); the mask is absent with ``return_mask=False``, the counts and
+        scores without a ground truth.  ``groundtruth``: the labels of the
+        shard's rows (nl, n2, n3), e.g. ``G[i0:i1]`` of the whole ground truth.
+        ``gt_device_ptr`` / ``mask_device_ptr`` (with ``ldG`` / ``ldP``, default
+        nl) take the labels from and write the mask to device memory instead
+        (TRITD_FG_DEVICE); the mask is then not returned.  The session's state
+        is untouched: a ``run`` after it continues as without it."""
+        nl, n2, n3 = self.i1 - self.i0, self.n2, self.n3
+        counts = np.zeros((n3, 4), dtype=np.int64)
+        mask = G = None
+        if gt_device_ptr is not None or mask_device_ptr is not None:
+            if groundtruth is not None:
+                raise ValueError("groundtruth (host) with device pointers: pass gt_device_ptr")
+            _lib.check_one_runtime("foreground(gt_device_ptr=...)")
+            gptr = C.c_void_p(int(gt_device_ptr)) if gt_device_ptr is not None else None
+            pptr = C.c_void_p(int(mask_device_ptr)) if mask_device_ptr is not None else None
+            ldG = nl if ldG is None else int(ldG)
+            ldP = nl if ldP is None else int(ldP)
+            flags, counted = _lib.FG_DEVICE, gptr is not None
+        else:
+            gptr, ldG = None, nl
+            if groundtruth is not None:
+                G, ldG = _label_bytes(groundtruth, (nl, n2, n3))
+                gptr = _ptr(G)
+            if return_mask:
+                mask = np.zeros((nl, n2, n3), dtype=np.uint8, order="F")
+            pptr, ldP, flags, counted = _ptr(mask), nl, 0, G is not None
+        check(self._fn("foreground")(self._s, float(thr), gptr, ldG, pptr, ldP, _ptr(counts), flags))
+        out = {}
+        if mask is not None:
+            out["mask"] = mask.view(np.bool_)
+        if counted:
+            out.update(counts=counts, **foreground_scores(counts, nl * n2 * n3))
+        return out
 
     def run(self, iters):
         check(self._fn("run")(self._s, int(iters)))
@@ -706,6 +814,13 @@ class Session(_SessionBase):
         if self._holdout:
             out.update(self.get_val())
         return out
+
+    def foreground_ms(self):
+        """ms of the kernel of the last ``foreground`` made with ``set_timing``
+        on (HIP events around its launch): tritd_session_foreground_ms."""
+        ms = C.c_double(0)
+        check(lib.tritd_session_foreground_ms(self._s, C.byref(ms)))
+        return ms.value
 
     def rre_parts(self, dX_ptr, ldX):
         _lib.check_one_runtime("Session.rre_parts")
@@ -946,6 +1061,6 @@ class Comm:
 __all__ = ["triple_decomp_ADMM", "triple_decomp_ADMM_outlier", "triple_decomp_ALS", "AlsSession",
            "NcvxSession",
            "triple_decomp_ncvx",
-           "make_als_opts", "evaluate", "quality_ybz", "triple_product", "unfold",
+           "make_als_opts", "evaluate", "quality_ybz", "foreground_eval", "foreground_scores", "triple_product", "unfold",
            "soft_threshold", "buildF", "buildG", "buildH", "Session", "Comm", "TritdError",
            "make_opts", "initial_factors", "PinvToleranceWarning"]

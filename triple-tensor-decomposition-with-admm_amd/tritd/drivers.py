@@ -107,7 +107,8 @@ def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0
 
 
 def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=None, C0=None,
-                 printer=print, name="data", save_dir=None, use_mask=False):
+                 printer=print, name="data", save_dir=None, use_mask=False, groundtruth=None,
+                 thr=50.0):
     """TRIPLE branch of video_triple_comparison.m (:26-76) through the
     `triple_decomp_ADMM_outlier` name the script calls (:54): RMSE/NRMSE of
     X_hat on the missing entries, of O on the observed ones, of X_hat + O on
@@ -116,7 +117,13 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     (variable Y, :32, every ratio) and, when missing_ratio == plot_rate == 0
     (:58), the errHist / X_hat / O .mat files of :59-61.  `use_mask` passes
     `observed = ~mask` to the solver, `use_mask="nan"` NaN-marked data and
-    `observed="nan"` (see traffic_triple)."""
+    `observed="nan"` (see traffic_triple).
+
+    `groundtruth` (CDnet labels of X's shape: 255 = motion, 170 = unknown) adds
+    the script's `eval` (:316-371) on the returned O with the threshold `thr`
+    (the reference's 50, :339): its five lines (:366-370) are printed after the
+    line above and the result gains `precision, recall, f1, pwc, fg_counts`
+    (per frame: TP, FP, FN, TN) and `fg_mask`.  Without it nothing changes."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     rng = np.random.default_rng(seed)
     mask = missing_mask(X.shape, missing_ratio, rng)
@@ -147,9 +154,20 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     printer("TRIPLE ADMM - RMSE: %.4e, NRMSE: %.4e, SRMSE: %.4e, SNRMSE: %.4e, TRMSE: %.4e, "
             "TNRMSE: %.4e, PSNR: %.4e, SSIM: %.4e, Time: %.2f s"
             % (rmse, nrmse, rmse2, nrmse2, rmse3, nrmse3, psnr, ssim, timer))
-    return dict(A=A, B=B, C=C, O=O, errHist=errHist, X_hat=X_hat, mask=mask, rmse=rmse,
-                nrmse=nrmse, srmse=rmse2, snrmse=nrmse2, trmse=rmse3, tnrmse=nrmse3, psnr=psnr,
-                ssim=ssim, time=timer)
+    out = dict(A=A, B=B, C=C, O=O, errHist=errHist, X_hat=X_hat, mask=mask, rmse=rmse,
+               nrmse=nrmse, srmse=rmse2, snrmse=nrmse2, trmse=rmse3, tnrmse=nrmse3, psnr=psnr,
+               ssim=ssim, time=timer)
+    if groundtruth is not None:  # eval(X, groundtruth, X_hat, O)  (:316-371)
+        fg = api.foreground_eval(O, groundtruth, thr)
+        TP, FP, FN, TN = (int(v) for v in fg["total"])
+        printer("TP: %d FP: %d TN: %d FN: %d " % (TP, FP, TN, FN))   # :366
+        printer("Precision: %.4f" % fg["precision"])                 # :367
+        printer("Recall   : %.4f" % fg["recall"])                    # :368
+        printer("F1 Score : %.4f" % fg["f1"])                        # :369
+        printer("PWC      : %.4f%%" % fg["pwc"])                     # :370
+        out.update(precision=fg["precision"], recall=fg["recall"], f1=fg["f1"], pwc=fg["pwc"],
+                   fg_counts=fg["counts"], fg_mask=fg["mask"])
+    return out
 
 
 def holdout_mask(observed, ratio, rng):
