@@ -769,6 +769,61 @@ tritd_status tritd_foreground_scores(const int64_t* counts, int64_t nf, int64_t 
                                      int64_t total[4], double* precision, double* recall,
                                      double* f1, double* pwc);
 
+/* The video driver's report from a session: what
+ * video_triple_comparison.m:56,64-67 computes after the solve, from the
+ * session's resident tensors.  Notation: X the original tensor of the shard
+ * (double, column-major, fibres ldX apart), m the byte mask of missing entries
+ * (nonzero = missing, laid out like X with fibres ldM bytes apart; NULL:
+ * nothing is missing), L the triple product of the session's current factors
+ * (:56), O what tritd_session_get / tritd_als_session_get_O would return at
+ * that moment.  The call returns raw parts, as tritd_session_rre_parts does,
+ * so that a caller with several shards adds them:
+ *   sums[0] = sum_m (L-X)^2     sums[1] = sum_m X^2       evaluate(X_hat, gt, mask)   :64
+ *   sums[2] = sum_~m (O-X)^2    sums[3] = sum_~m X^2      evaluate(O, gt_2, ~mask)    :65
+ *   sums[4] = sum ((L+O)-X)^2   sums[5] = sum X^2         evaluate(X_hat+O, X, true)  :66
+ *   frame_sq[t]   = sum_ij (L-X)^2 of frame t, t < n3     psnr_index's numerator      :67
+ *   frame_ssim[t] = ssim_index(X(:,:,t), L(:,:,t))        quality_ybz                 :67
+ * frame_ssim[t] is -Inf when a frame is smaller than the 11 x 11 window, as
+ * tritd_quality_f64 gives.  The figures follow on the host (evaluate, :290-298):
+ * rmse = sqrt(S0), nrmse = sqrt(S0)/sqrt(S1), likewise srmse/snrmse from S2, S3
+ * and trmse/tnrmse from S4, S5 (0/0 = NaN, as MATLAB gives for an empty gt);
+ * psnr = mean_t 10 log10(255^2 / (frame_sq[t]/(n1 n2))), ssim = mean_t
+ * frame_ssim[t].  An ADMM session before its first iteration and an ALS
+ * session that is not nonconvex have O = 0: then S2 = S3 and S4 = sum (L-X)^2.
+ * A masked session has O = 0 at its unobserved entries.
+ *
+ * Every sum is a fixed-order tree (no floating-point atomics): two calls give
+ * the same bits.  Padding is never read from X or m.  sums (6 doubles),
+ * frame_sq and frame_ssim (n3 doubles each) are host memory; sums or frame_sq
+ * may be NULL, not both; frame_ssim == NULL means no SSIM and no scratch, else
+ * the pass also writes L into a scratch of (i1-i0) n2 n3 doubles.  With
+ * TRITD_REPORT_DEVICE in flags X and missing are device pointers on the
+ * session's device, else host pointers staged through device buffers.  The
+ * call waits for the session stream and writes nothing of the session: a run
+ * after it continues bit for bit.
+ * Errors, each before the first HIP call and in this order: NULL session, NULL
+ * X, ldX < i1-i0, ldM < i1-i0 with a mask, sums and frame_sq both NULL (all
+ * TRITD_ERR_ARG); an fp32 session (TRITD_ERR_UNSUPPORTED); frame_ssim on a
+ * session that does not hold all rows (i0 > 0 or i1 < n1: the window crosses
+ * row shards; TRITD_ERR_ARG, the sums and frame_sq still work there).  A
+ * failed scratch allocation is TRITD_ERR_NOMEM. */
+enum { TRITD_REPORT_DEVICE = 1u }; /* X and missing are device pointers on the session's device */
+tritd_status tritd_session_report(tritd_session* s, const double* X, int64_t ldX,
+                                  const uint8_t* missing, int64_t ldM, double* sums,
+                                  double* frame_sq, double* frame_ssim, uint32_t flags);
+/* The same (video_triple_comparison.m:56,64-67) on an ALS session: O is that
+ * of tritd_als_session_get_O (iteration k-1 after a stop) for a nonconvex
+ * session and 0 otherwise. */
+tritd_status tritd_als_session_report(tritd_als_session* s, const double* X, int64_t ldX,
+                                      const uint8_t* missing, int64_t ldM, double* sums,
+                                      double* frame_sq, double* frame_ssim, uint32_t flags);
+/* ms of the kernels of the last tritd_session_report (the pass of
+ * video_triple_comparison.m:56,64-67, its reduction and, with frame_ssim, the
+ * SSIM kernels) made while tritd_session_set_timing was on, from HIP events
+ * around them: the staging copies and the wait are not in it.  0 before the
+ * first such call. */
+tritd_status tritd_session_report_ms(tritd_session* s, double* kernel_ms);
+
 /* Device-pointer variants (for device-resident callers and the bench). */
 tritd_status tritd_dev_unfold_f64(const double* X, int64_t n1, int64_t n2, int64_t n3, int32_t mode,
                                   double* Xn, void* stream);

@@ -515,4 +515,14 @@ void AlsSession::foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t*
                    });
 }
 
+void AlsSession::report(const ReportCall& c) {
+    int done = 0, stopped = 0;
+    sync(&done, &stopped);
+    RpArgs a;
+    a.Ah = Ah_.p; a.Bh = Bh_.p; a.ChT = ChT_.p;
+    const int kk = stopped ? done - 1 : done;  // the O of get_O
+    if (ncvx_) a.D = (kk & 1) ? Ob_.p : Oa_.p;
+    run_report(g_, ncvx_ ? RP_STORED64 : RP_ZERO, a, c, st_, nullptr);
+}
+
 }  // namespace tritd

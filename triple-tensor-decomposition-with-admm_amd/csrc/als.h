@@ -102,6 +102,9 @@ class AlsSession {
     // Session::foreground (solver.h) on the O of get_O, read where it is stored
     void foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t* pred, int64_t ldP,
                     int64_t* counts, bool on_device);
+    // Session::report (solver.h) on the current factors and the O of get_O
+    // (k - 1 after a stop); a session that is not nonconvex has O = 0
+    void report(const ReportCall& c);
 
     // --- phase interface (device groups drive these; see api.cpp) -------
     int next_iter();

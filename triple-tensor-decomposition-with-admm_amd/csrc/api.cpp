@@ -1942,4 +1942,58 @@ tritd_status tritd_foreground_scores(const int64_t* counts, int64_t nf, int64_t 
     });
 }
 
+// ---------------------------------------------------------------------------
+// the video driver's report (video_triple_comparison.m:56,64-67)
+// ---------------------------------------------------------------------------
+// X, the leading dimensions, the outputs, then what the session cannot do:
+// every rule before the first HIP call, in this order
+static ReportCall report_call(const Geom& g, bool f32, const double* X, int64_t ldX,
+                              const uint8_t* missing, int64_t ldM, double* sums, double* frame_sq,
+                              double* frame_ssim, uint32_t flags, const std::vector<double>& win) {
+    need(X, "X");
+    if (ldX < g.n1l) throw Error(TRITD_ERR_ARG, "ldX smaller than the shard");
+    if (missing && ldM < g.n1l) throw Error(TRITD_ERR_ARG, "ldM smaller than the shard");
+    if (!sums && !frame_sq)
+        throw Error(TRITD_ERR_ARG, "sums and frame_sq are both NULL: nothing to compute");
+    if (f32) throw Error(TRITD_ERR_UNSUPPORTED, "report: fp64 sessions only");
+    if (frame_ssim && (g.i0 > 0 || g.i1 < g.n1))  // ssim_index's window crosses row shards
+        throw Error(TRITD_ERR_ARG, "frame_ssim needs a session that holds all rows");
+    ReportCall c;
+    c.X = X; c.ldX = ldX; c.missing = missing; c.ldM = ldM;
+    c.sums = sums; c.frame_sq = frame_sq; c.frame_ssim = frame_ssim;
+    c.win = frame_ssim ? win.data() : nullptr;
+    c.on_device = (flags & TRITD_REPORT_DEVICE) != 0;
+    return c;
+}
+
+tritd_status tritd_session_report(tritd_session* s, const double* X, int64_t ldX,
+                                  const uint8_t* missing, int64_t ldM, double* sums,
+                                  double* frame_sq, double* frame_ssim, uint32_t flags) {
+    return guarded([&] {
+        Session* S = admm(s);
+        const std::vector<double> win = frame_ssim ? ssim_window() : std::vector<double>();
+        S->report(report_call(S->geom(), S->is_f32(), X, ldX, missing, ldM, sums, frame_sq,
+                              frame_ssim, flags, win));
+    });
+}
+
+tritd_status tritd_als_session_report(tritd_als_session* s, const double* X, int64_t ldX,
+                                      const uint8_t* missing, int64_t ldM, double* sums,
+                                      double* frame_sq, double* frame_ssim, uint32_t flags) {
+    return guarded([&] {
+        AlsSession* as = als(s);
+        const std::vector<double> win = frame_ssim ? ssim_window() : std::vector<double>();
+        as->report(report_call(as->geom(), false, X, ldX, missing, ldM, sums, frame_sq, frame_ssim,
+                               flags, win));
+    });
+}
+
+tritd_status tritd_session_report_ms(tritd_session* s, double* kernel_ms) {
+    return guarded([&] {
+        Session* S = admm(s);
+        need(kernel_ms, "kernel_ms");
+        *kernel_ms = S->report_ms();
+    });
+}
+
 }  // extern "C"

@@ -400,4 +400,38 @@ size_t quality_scratch(int64_t n1, int64_t n2, int64_t nf) {
     return (size_t)((nsq + nss) * nf);
 }
 
+// The SSIM half of launch_quality alone (the session report, DESIGN.md §17,
+// has frame_sq from its own pass): the same tile kernel and the same finish
+// with no squared-difference partials, whose psnr output (+Inf) goes to the
+// nf doubles at the end of the scratch and is dropped.
+void launch_ssim(const double* X, const double* Y, int64_t n1, int64_t n2, int64_t nf,
+                 const double* win, double C1, double C2, double* scratch, double* ssim,
+                 hipStream_t st) {
+    const int64_t fsz = n1 * n2;
+    const bool small = n1 < QW || n2 < QW;
+    const unsigned gx = small ? 0u : (unsigned)cdiv(n1 - (QW - 1), QT);
+    const unsigned gy = small ? 0u : (unsigned)cdiv(n2 - (QW - 1), QT);
+    const int nss = (int)(gx * gy);
+    const double nmap = small ? 1.0 : (double)((n1 - (QW - 1)) * (n2 - (QW - 1)));
+    double* unused = scratch + (size_t)nss * nf;
+    constexpr int64_t QF = 65535;  // (launch_quality: frames per launch)
+    for (int64_t f0 = 0; f0 < nf; f0 += QF) {
+        const int64_t nb = nf - f0 < QF ? nf - f0 : QF;
+        double* ssb = scratch + (size_t)nss * f0;
+        if (!small) {
+            hipLaunchKernelGGL(k_ssim_tiles, dim3(gx, gy, (unsigned)nb), dim3(QT * QT), 0, st,
+                               X + f0 * fsz, Y + f0 * fsz, n1, n2, win, C1, C2, ssb);
+            TRITD_CHECK_LAUNCH();
+        }
+        hipLaunchKernelGGL(k_quality_finish, dim3((unsigned)nb), dim3(64), 0, st, ssb, 0, ssb, nss,
+                           (double)fsz, nmap, (int)small, unused + f0, ssim + f0);
+        TRITD_CHECK_LAUNCH();
+    }
+}
+
+size_t ssim_scratch(int64_t n1, int64_t n2, int64_t nf) {
+    const int64_t nss = (n1 < QW || n2 < QW) ? 0 : cdiv(n1 - (QW - 1), QT) * cdiv(n2 - (QW - 1), QT);
+    return (size_t)((nss + 1) * nf);
+}
+
 }  // namespace tritd

@@ -395,6 +395,75 @@ void run_foreground(int64_t rows, int64_t cols, int64_t nf, const uint8_t* gt, i
                                              unsigned long long*)>& launch,
                     double* kernel_ms = nullptr);
 
+// ---- the video driver's report from a session (k_report.hip) ----
+// video_triple_comparison.m:56,64-67 in one pass over the shard: with L the
+// triple product of the factors, O by RpSource, X the original and m the byte
+// mask of missing entries (null: none),
+//   sums[0..5] = sum_m (L-X)^2, sum_m X^2, sum_~m (O-X)^2, sum_~m X^2,
+//                sum ((L+O)-X)^2, sum X^2
+//   frame_sq[t] = sum_ij (L-X)^2 of frame t          (psnr_index's numerator)
+// and, with Lout, L column-major (fibres n1l apart) for the SSIM kernels.
+// Every sum is a fixed-order tree: two calls give the same bits.
+enum RpSource {
+    RP_ADMM64 = 0,    // (D + invL_next Y_L) - T of an fp64 ADMM session (o_expr.h), 0 where M says unobserved
+    RP_STORED64 = 1,  // a stored tile-major tensor, passed as D
+    RP_ZERO = 2       // O = 0: nothing is read
+};
+struct RpArgs {
+    // the Khatri-Rao operands of launch_tp (ahj, bhj: its strides; bhj < 0: RP)
+    const double* Ah = nullptr;
+    const double* Bh = nullptr;
+    const double* ChT = nullptr;
+    int64_t ahj = 0, bhj = -1;
+    const double* D = nullptr;
+    const double* YL = nullptr;
+    const double* T = nullptr;  // TX order
+    double invL_next = 0.0;
+    const unsigned long long* M = nullptr;  // mask words (common.h: MK) or null
+    // column-major tensors of the shard: element (i, j, t) at i + ld (j + n2 t)
+    const double* X = nullptr;
+    int64_t ldX = 0;
+    const uint8_t* missing = nullptr;
+    int64_t ldM = 0;
+    double* Lout = nullptr;
+    // [grid][6] and [grid][n3] block partials (report_grid(g) workgroups)
+    double* part = nullptr;
+    double* fpart = nullptr;
+    // filled by the launcher from the geometry
+    int64_t n1l = 0, n1p = 0, n2 = 0, n3 = 0, n3p = 0, tiles = 0, ntt = 0;
+};
+int report_grid(const Geom& g);
+// the pass and the reduction of its partials into sums6[6] and frame_sq[n3] (device)
+void launch_report(const Geom& g, int src, const RpArgs& a, double* sums6, double* frame_sq,
+                   hipStream_t st);
+// One call's host side, shared by the two session classes.  X and missing are
+// host pointers staged through device buffers, or (on_device) device pointers
+// used where they lie; sums[6], frame_sq[n3], frame_ssim[n3] are host outputs
+// (each may be null; frame_ssim null: no SSIM and no scratch; win: the 11 x 11
+// window of ssim_index on the host, needed with frame_ssim).  Every device
+// buffer is allocated before the first launch, so a failed allocation leaves
+// nothing enqueued.  Waits for the stream.  kernel_ms (or null): the time of
+// the kernels alone, from events around them.
+struct ReportCall {
+    const double* X = nullptr;
+    int64_t ldX = 0;
+    const uint8_t* missing = nullptr;
+    int64_t ldM = 0;
+    double* sums = nullptr;
+    double* frame_sq = nullptr;
+    double* frame_ssim = nullptr;
+    const double* win = nullptr;
+    bool on_device = false;
+};
+void run_report(const Geom& g, int src, RpArgs a, const ReportCall& c, hipStream_t st,
+                double* kernel_ms);
+// ssim_index of each frame alone (launch_quality without its PSNR half; the
+// same kernels, so the same bits): scratch of ssim_scratch() doubles
+size_t ssim_scratch(int64_t n1, int64_t n2, int64_t nf);
+void launch_ssim(const double* X, const double* Y, int64_t n1, int64_t n2, int64_t nf,
+                 const double* win, double C1, double C2, double* scratch, double* ssim,
+                 hipStream_t st);
+
 // ---------------------------------------------------------------------------
 // fp32 data path (D of class single): T, O, E, Y_L, Y_O, W and
 // the mode contractions in fp32; factors, Grams and solves in fp64.

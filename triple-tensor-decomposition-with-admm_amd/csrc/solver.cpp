@@ -1421,6 +1421,26 @@ void Session::foreground(double thr, const uint8_t* gt, int64_t ldG, uint8_t* pr
                    timing_ ? &fg_ms_ : nullptr);
 }
 
+void Session::report(const ReportCall& c) {
+    if (f32_) throw Error(TRITD_ERR_UNSUPPORTED, "report: fp64 sessions only");
+    int done = 0;
+    sync(&done, nullptr);
+    RpArgs a;
+    const double* ah = finished_ah(done);
+    if (qi_) {  // the materialised H operand and its strides, as rre_parts
+        launch_qi_h(g_, g_.r, ah, Bh_.p, H_.p, nullptr, st_);
+        a.Ah = H_.p; a.Bh = ones_.p; a.ahj = g_.n1p * g_.RP; a.bhj = 0;
+    } else {
+        a.Ah = ah; a.Bh = Bh_.p;
+    }
+    a.ChT = ChT_.p;
+    // the scalar and the mask words of get()'s fix-up; O is 0 before the first iteration
+    a.D = D_.p; a.YL = YL_.p; a.T = T_.p;
+    if (done > 0) a.invL_next = 1.0 / mu_[(size_t)done];
+    a.M = mask_words();
+    run_report(g_, done == 0 ? RP_ZERO : RP_ADMM64, a, c, st_, timing_ ? &rp_ms_ : nullptr);
+}
+
 void Session::get_val(double* valHist, double* valHist1, int* best_iter, int* stop_reason) {
     int done = 0;
     sync(&done, nullptr);

@@ -173,6 +173,15 @@ class Session {
     // ms of the kernel of the last foreground() made with timing on (events
     // around its launch; 0 before the first)
     double foreground_ms() const { return fg_ms_; }
+    // The video driver's figures (video_triple_comparison.m:56,64-67;
+    // DESIGN.md §17) on the current factors and the O that get() would return
+    // now: the raw sums, frame squares and SSIM frames of ReportCall
+    // (kernels.h), over the shard's rows.  fp64 sessions.  Nothing of the
+    // session is written (the Qi model refreshes its H operand, which every
+    // iteration rebuilds before use, as rre_parts does); waits for the stream.
+    void report(const ReportCall& c);
+    // ms of the kernels of the last report() made with timing on (0 before the first)
+    double report_ms() const { return rp_ms_; }
     // doubles of red3 reduced over the shards at creation (normD^2, the fit
     // count; holdout: + ||H o Omega o D||^2, the held-out count, sum |.|) and in
     // every iteration of the phase schedules (holdout: + the two score sums)
@@ -371,6 +380,7 @@ class Session {
 
     int timing_ = 0;
     double fg_ms_ = 0.0;
+    double rp_ms_ = 0.0;
     // timing event `slot` of this iteration (null: not timed), and its record
     hipEvent_t ev_slot(int slot) const {
         return timing_ ? ev_[ev_.size() - EV_SLOTS + slot] : nullptr;

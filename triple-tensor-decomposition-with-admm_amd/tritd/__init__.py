@@ -21,6 +21,7 @@ from .api import (  # noqa: F401
     initial_factors,
     make_opts,
     quality_ybz,
+    report_scores,
     soft_threshold,
     triple_decomp_ADMM,
     triple_decomp_ADMM_outlier,

@@ -34,6 +34,7 @@ SESSION_F32 = 2
 SESSION_PROBE = 4
 FLAG_PINV_TOL = 1  # TRITD_FLAG_PINV_TOL (include/tritd.h)
 FG_DEVICE = 1  # TRITD_FG_DEVICE (include/tritd.h)
+REPORT_DEVICE = 1  # TRITD_REPORT_DEVICE
 
 
 class TritdError(RuntimeError):
@@ -185,6 +186,10 @@ SIGNATURES = {
     "tritd_dev_foreground_f32": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_double, vp, i64, vp,
                                            vp]),
     "tritd_foreground_scores": (C.c_int, [vp, i64, i64, vp, dp, dp, dp, dp]),
+    # the video driver's report from a session (video_triple_comparison.m:56,64-67)
+    "tritd_session_report": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_uint32]),
+    "tritd_als_session_report": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, vp, C.c_uint32]),
+    "tritd_session_report_ms": (C.c_int, [vp, dp]),
 }
 
 # Entry points whose name carries a MATLAB variable's capital letter.  Bound

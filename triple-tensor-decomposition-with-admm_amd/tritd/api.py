@@ -552,6 +552,49 @@ def foreground_eval(F, groundtruth=None, thr=50.0):
     return out
 
 
+def _in_place(a, shape, dtype):
+    """``a`` as a column-major (nl, n2, n3) array of ``dtype`` with a leading
+    dimension: rows i0:i1 of a whole column-major tensor are used where they
+    lie (their strides give ld), anything else is copied.
+    -> (array to keep alive, leading dimension in elements)"""
+    a = np.asarray(a)
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError(f"expected the shape {tuple(shape)}, got {tuple(a.shape)}")
+    es = np.dtype(dtype).itemsize
+    if a.dtype == np.dtype(dtype) and a.ndim == 3 and a.size and a.strides[0] == es:
+        ld = a.strides[1] // es
+        if ld >= a.shape[0] and a.strides == (es, ld * es, ld * es * a.shape[1]):
+            return a, int(ld)
+    a = np.asfortranarray(a, dtype=dtype)
+    return a, int(a.shape[0])
+
+
+def report_scores(sums, frame_sq, frame_ssim, n1, n2):
+    """The eight figures of video_triple_comparison.m:64-67 from the raw parts
+    of ``Session.report`` (tritd_session_report), on the host: a caller with
+    several shards adds their ``sums`` and ``frame_sq`` first.  evaluate
+    (:290-298): rmse = sqrt(S0), nrmse = sqrt(S0)/sqrt(S1), srmse/snrmse from
+    S2, S3, trmse/tnrmse from S4, S5; 0/0 is NaN, as MATLAB gives for an empty
+    gt.  psnr_index: psnr_frames = 10 log10(255^2 / (frame_sq / (n1 n2))), psnr
+    and ssim the means over the frames (quality_ybz).  ``frame_ssim`` None:
+    ssim is NaN and ssim_frames None.  ``n1, n2``: the size of a whole frame."""
+    S = np.asarray(sums, dtype=np.float64).reshape(6)
+    fsq = np.asarray(frame_sq, dtype=np.float64).reshape(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        root = np.sqrt(S)
+        out = dict(rmse=float(root[0]), nrmse=float(root[0] / root[1]),
+                   srmse=float(root[2]), snrmse=float(root[2] / root[3]),
+                   trmse=float(root[4]), tnrmse=float(root[4] / root[5]))
+        pf = 10.0 * np.log10(255.0 ** 2 / (fsq / float(n1 * n2)))
+    out.update(psnr=float(np.mean(pf)), psnr_frames=pf)
+    if frame_ssim is None:
+        out.update(ssim=float("nan"), ssim_frames=None)
+    else:
+        sf = np.asarray(frame_ssim, dtype=np.float64).reshape(-1)
+        out.update(ssim=float(np.mean(sf)), ssim_frames=sf)
+    return out
+
+
 def _design(which, P, Q, nP, nQ, r):
     out = np.zeros((r * r, nP * nQ), order="F")
     check(lib.tritd_build_design_f64(which.encode(), _ptr(P), _ptr(Q), nP, nQ, r, _ptr(out)))
@@ -703,6 +746,57 @@ class _SessionBase:
             out.update(counts=counts, **foreground_scores(counts, nl * n2 * n3))
         return out
 
+    def report(self, X=None, missing=None, *, ssim=True, x_device_ptr=None,
+               missing_device_ptr=None, ldX=None, ldM=None):
+        """The figures video_triple_comparison.m:64-67 prints, from the
+        session's resident tensors (tritd_session_report /
+        tritd_als_session_report): with L the triple product of
+        the current factors and O what ``get()`` / ``get_O()`` would return now
+        (0 for a plain ALS session and before the first ADMM iteration),
+        ``rmse, nrmse`` of L on the missing entries, ``srmse, snrmse`` of O on
+        the others, ``trmse, tnrmse`` of L + O on all, ``psnr, ssim`` of L
+        against X with ``psnr_frames, ssim_frames``, and the raw ``sums`` (6)
+        and ``frame_sq`` (n3) they come from (``report_scores``; a caller with
+        several shards adds those).  Neither L nor O is materialised or
+        downloaded.  ``X``: the original tensor of the shard's rows (nl, n2,
+        n3), e.g. ``X[i0:i1]`` of the whole tensor, used where it lies;
+        ``missing``: a logical array of the same shape, True = missing (None:
+        nothing is).  ``x_device_ptr`` / ``missing_device_ptr`` (with ``ldX`` /
+        ``ldM``, default nl) take them from device memory instead
+        (TRITD_REPORT_DEVICE).  ``ssim=False`` skips SSIM and its scratch; a
+        session that does not hold all rows must (TRITD_ERR_ARG otherwise).
+        fp64 sessions.  The session's state is untouched."""
+        nl, n2, n3 = self.i1 - self.i0, self.n2, self.n3
+        if x_device_ptr is not None:
+            if X is not None or missing is not None:
+                raise ValueError("X / missing (host) with x_device_ptr: pass device pointers")
+            _lib.check_one_runtime("report(x_device_ptr=...)")
+            xptr = C.c_void_p(int(x_device_ptr))
+            mptr = C.c_void_p(int(missing_device_ptr)) if missing_device_ptr is not None else None
+            ldX = nl if ldX is None else int(ldX)
+            ldM = nl if ldM is None else int(ldM)
+            flags, keep = _lib.REPORT_DEVICE, ()
+        else:
+            if X is None or missing_device_ptr is not None:
+                raise ValueError("report needs X, or x_device_ptr with missing_device_ptr")
+            Xa, ldX = _in_place(X, (nl, n2, n3), np.float64)
+            xptr, mptr, ldM, keep = _ptr(Xa), None, nl, (Xa,)
+            if missing is not None:
+                m = np.asarray(missing)
+                if m.dtype.itemsize != 1:
+                    m = m != 0
+                Ma, ldM = _in_place(m.view(np.uint8), (nl, n2, n3), np.uint8)
+                mptr, keep = _ptr(Ma), (Xa, Ma)
+            flags = 0
+        sums, fsq = np.zeros(6), np.zeros(n3)
+        fss = np.zeros(n3) if ssim else None
+        check(self._fn("report")(self._s, xptr, ldX, mptr, ldM, _ptr(sums), _ptr(fsq), _ptr(fss),
+                                 flags))
+        del keep
+        out = report_scores(sums, fsq, fss, self.n1, n2)
+        out.update(sums=sums, frame_sq=fsq)
+        return out
+
     def run(self, iters):
         check(self._fn("run")(self._s, int(iters)))
 
@@ -820,6 +914,13 @@ class Session(_SessionBase):
         on (HIP events around its launch): tritd_session_foreground_ms."""
         ms = C.c_double(0)
         check(lib.tritd_session_foreground_ms(self._s, C.byref(ms)))
+        return ms.value
+
+    def report_ms(self):
+        """ms of the kernels of the last ``report`` made with ``set_timing``
+        on (HIP events around them): tritd_session_report_ms."""
+        ms = C.c_double(0)
+        check(lib.tritd_session_report_ms(self._s, C.byref(ms)))
         return ms.value
 
     def rre_parts(self, dX_ptr, ldX):
@@ -1061,6 +1162,6 @@ class Comm:
 __all__ = ["triple_decomp_ADMM", "triple_decomp_ADMM_outlier", "triple_decomp_ALS", "AlsSession",
            "NcvxSession",
            "triple_decomp_ncvx",
-           "make_als_opts", "evaluate", "quality_ybz", "foreground_eval", "foreground_scores", "triple_product", "unfold",
+           "make_als_opts", "evaluate", "quality_ybz", "foreground_eval", "foreground_scores", "report_scores", "triple_product", "unfold",
            "soft_threshold", "buildF", "buildG", "buildH", "Session", "Comm", "TritdError",
            "make_opts", "initial_factors", "PinvToleranceWarning"]

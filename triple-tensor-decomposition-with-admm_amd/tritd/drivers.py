@@ -108,7 +108,7 @@ def traffic_triple(X, r=5, missing_ratio=0.15, *, opts=None, seed=0, A0=None, B0
 
 def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=None, C0=None,
                  printer=print, name="data", save_dir=None, use_mask=False, groundtruth=None,
-                 thr=50.0):
+                 thr=50.0, session=False):
     """TRIPLE branch of video_triple_comparison.m (:26-76) through the
     `triple_decomp_ADMM_outlier` name the script calls (:54): RMSE/NRMSE of
     X_hat on the missing entries, of O on the observed ones, of X_hat + O on
@@ -123,7 +123,13 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     the script's `eval` (:316-371) on the returned O with the threshold `thr`
     (the reference's 50, :339): its five lines (:366-370) are printed after the
     line above and the result gains `precision, recall, f1, pwc, fg_counts`
-    (per frame: TP, FP, FN, TN) and `fg_mask`.  Without it nothing changes."""
+    (per frame: TP, FP, FN, TN) and `fg_mask`.  Without it nothing changes.
+
+    `session=True` solves through a `Session` and takes the eight figures from
+    `Session.report` (and, with `groundtruth`, the foreground scores from
+    `Session.foreground`) while the tensors are still on the device: X_hat and
+    O are downloaded only for the returned dict and the .mat files.  The same
+    lines are printed in the same format.  With the default nothing changes."""
     X = np.asfortranarray(np.asarray(X, dtype=np.float64))
     rng = np.random.default_rng(seed)
     mask = missing_mask(X.shape, missing_ratio, rng)
@@ -136,6 +142,9 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     gt = X.ravel(order="F")[mask.ravel(order="F")]       # X(mask_missing), column-major (:36)
     gt_2 = X.ravel(order="F")[~mask.ravel(order="F")]    # X(~mask_missing)              (:37)
     o = dict(VIDEO_OPTS if opts is None else opts)
+    if session:
+        return _video_triple_session(X, Y, mask, r, o, A0, B0, C0, observed if use_mask else None,
+                                     printer, name, save_dir, missing_ratio, groundtruth, thr)
     t0 = time.perf_counter()
     A, B, C, O, errHist = api.triple_decomp_ADMM_outlier(Y, r, o, A0, B0, C0,
                                                          **(dict(observed=observed) if use_mask else {}))
@@ -151,22 +160,66 @@ def video_triple(X, r=5, missing_ratio=0.0, *, opts=None, seed=0, A0=None, B0=No
     rmse2, nrmse2 = api.evaluate(O, gt_2, ~mask)
     rmse3, nrmse3 = api.evaluate(np.asfortranarray(X_hat + O), X)
     psnr, ssim = api.quality_ybz(X, X_hat)
-    printer("TRIPLE ADMM - RMSE: %.4e, NRMSE: %.4e, SRMSE: %.4e, SNRMSE: %.4e, TRMSE: %.4e, "
-            "TNRMSE: %.4e, PSNR: %.4e, SSIM: %.4e, Time: %.2f s"
-            % (rmse, nrmse, rmse2, nrmse2, rmse3, nrmse3, psnr, ssim, timer))
+    printer(_VIDEO_LINE % (rmse, nrmse, rmse2, nrmse2, rmse3, nrmse3, psnr, ssim, timer))
     out = dict(A=A, B=B, C=C, O=O, errHist=errHist, X_hat=X_hat, mask=mask, rmse=rmse,
                nrmse=nrmse, srmse=rmse2, snrmse=nrmse2, trmse=rmse3, tnrmse=nrmse3, psnr=psnr,
                ssim=ssim, time=timer)
     if groundtruth is not None:  # eval(X, groundtruth, X_hat, O)  (:316-371)
-        fg = api.foreground_eval(O, groundtruth, thr)
-        TP, FP, FN, TN = (int(v) for v in fg["total"])
-        printer("TP: %d FP: %d TN: %d FN: %d " % (TP, FP, TN, FN))   # :366
-        printer("Precision: %.4f" % fg["precision"])                 # :367
-        printer("Recall   : %.4f" % fg["recall"])                    # :368
-        printer("F1 Score : %.4f" % fg["f1"])                        # :369
-        printer("PWC      : %.4f%%" % fg["pwc"])                     # :370
-        out.update(precision=fg["precision"], recall=fg["recall"], f1=fg["f1"], pwc=fg["pwc"],
-                   fg_counts=fg["counts"], fg_mask=fg["mask"])
+        _print_foreground(api.foreground_eval(O, groundtruth, thr), printer, out)
+    return out
+
+
+_VIDEO_LINE = ("TRIPLE ADMM - RMSE: %.4e, NRMSE: %.4e, SRMSE: %.4e, SNRMSE: %.4e, TRMSE: %.4e, "
+               "TNRMSE: %.4e, PSNR: %.4e, SSIM: %.4e, Time: %.2f s")
+
+
+def _print_foreground(fg, printer, out):
+    TP, FP, FN, TN = (int(v) for v in fg["total"])
+    printer("TP: %d FP: %d TN: %d FN: %d " % (TP, FP, TN, FN))   # :366
+    printer("Precision: %.4f" % fg["precision"])                 # :367
+    printer("Recall   : %.4f" % fg["recall"])                    # :368
+    printer("F1 Score : %.4f" % fg["f1"])                        # :369
+    printer("PWC      : %.4f%%" % fg["pwc"])                     # :370
+    out.update(precision=fg["precision"], recall=fg["recall"], f1=fg["f1"], pwc=fg["pwc"],
+               fg_counts=fg["counts"], fg_mask=fg["mask"])
+
+
+def _video_triple_session(X, Y, mask, r, o, A0, B0, C0, observed, printer, name, save_dir,
+                          missing_ratio, groundtruth, thr):
+    """video_triple(session=True): the solve of :54 as a Session run to
+    maxIter, the figures of :64-67 from Session.report and eval (:316-371)
+    from Session.foreground, on the device; then the downloads for the caller."""
+    n1, n2, n3 = X.shape
+    start = dict(A0=A0, B0=B0, C0=C0) if all(a is not None for a in (A0, B0, C0)) else o
+    A0, B0, C0 = api.initial_factors(n1, n2, n3, int(r), start)
+    t0 = time.perf_counter()
+    s = api.Session(int(r), o, A0, B0, C0, n1=n1, n2=n2, n3=n3, D=Y, probe=False,
+                    observed=observed)
+    try:
+        s.run(s.maxIter)
+        s.sync()
+        timer = time.perf_counter() - t0
+        # with no missing entries S0 = S1 = 0: rmse 0 and nrmse = 0/0 = NaN, as in MATLAB
+        rep = s.report(X, mask if mask.any() else None)
+        fg = s.foreground(thr, groundtruth) if groundtruth is not None else None
+        g = s.get()
+    finally:
+        s.close()
+    A, B, C, O, errHist = g["A"], g["B"], g["C"], g["O"], g["errHist"]
+    X_hat = api.triple_product(A, B, C)
+    if save_dir is not None and missing_ratio == 0:
+        from scipy.io import savemat
+        savemat(os.path.join(save_dir, "%s_triple_re_errHist.mat" % name), {"errHist": errHist})
+        savemat(os.path.join(save_dir, "%s_triple_re_Xhat.mat" % name), {"X_hat_re": X_hat})
+        savemat(os.path.join(save_dir, "%s_triple_re_O.mat" % name), {"O": O})
+    figures = tuple(rep[k] for k in ("rmse", "nrmse", "srmse", "snrmse", "trmse", "tnrmse", "psnr",
+                                     "ssim"))
+    printer(_VIDEO_LINE % (figures + (timer,)))
+    out = dict(A=A, B=B, C=C, O=O, errHist=errHist, X_hat=X_hat, mask=mask, time=timer,
+               **{k: rep[k] for k in ("rmse", "nrmse", "srmse", "snrmse", "trmse", "tnrmse", "psnr",
+                                      "ssim")})
+    if fg is not None:
+        _print_foreground(fg, printer, out)
     return out
 
 
