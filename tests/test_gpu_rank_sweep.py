@@ -82,11 +82,15 @@ def orc():
     return tritd_oracle
 
 
-def check(orc, got, case, label):
-    """check_solution of test_gpu_parity.py, printing each figure before it asserts."""
-    ref = sc.oracle_ref(case)
+def check(orc, got, case, label, ref=None, e_zero=False, model="cp"):
+    """check_solution of test_gpu_parity.py, printing each figure before it asserts.
+    ref: another reference than the sweep's own for `case` (tests/test_gpu_opts_ladder.py);
+    e_zero: E is identically zero on both sides where the caller's options make it so."""
+    if ref is None:
+        ref = sc.oracle_ref(case)
     A, B, C, O, eh, E, k = got
-    dev = dict(L=rel(orc.triple_product(A, B, C), orc.triple_product(ref["A"], ref["B"], ref["C"])),
+    dev = dict(L=rel(orc.triple_product(A, B, C, model),
+                     orc.triple_product(ref["A"], ref["B"], ref["C"], model)),
                O=rel(O, ref["O"]), E=rel(E, ref["E"]), A=rel(A, ref["A"]), B=rel(B, ref["B"]),
                C=rel(C, ref["C"]))
     n = min(len(eh), len(ref["errHist"]))
@@ -94,7 +98,10 @@ def check(orc, got, case, label):
     print("  sweep r=%s %s k=%d nnz(E)=%.3f " % (case, label, k, sc.nnz_share(E))
           + " ".join("%s=%.1e" % kv for kv in dev.items()), flush=True)
     assert k == ref["k"] and len(eh) == ref["k"]
-    assert np.any(ref["E"]) and np.any(E)
+    if e_zero:
+        assert not np.any(ref["E"]) and not np.any(E)
+    else:
+        assert np.any(ref["E"]) and np.any(E)
     assert dev["L"] <= TOL_LOE and dev["O"] <= TOL_LOE and dev["E"] <= TOL_LOE, dev
     assert dev["A"] <= TOL_ABC and dev["B"] <= TOL_ABC and dev["C"] <= TOL_ABC, dev
     np.testing.assert_allclose(eh, ref["errHist"], rtol=TOL_ERR, atol=ATOL_ERR)
